@@ -6,14 +6,21 @@ helicopter RK4, reward, flags, auto-reset) with actions read from HBM.  Workload
 configs[2]): 65 536 HeliHover-v0 envs per GPU, Dryden turbulence on (level 1), dt = 0.01 s, fp32,
 U(-1,1) random actions (a Philox-generated bank resident in HBM before timing), auto-reset on.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (one rank per GPU)
 
 `--gpus N` without a torch.distributed launcher starts one itself (a child process; this parent
 never touches the GPU).  Prints ONE JSON line on rank 0.  Envs shard with no data-path collective
-(weak scaling).  With N > 1 the line also carries BASELINE config 5 (1 048 576 envs sharded over
-the ranks, observations gathered to rank 0 over RCCL every step) with and without the gather;
-`--gather-obs` makes that the headline instead.
+(weak scaling).
+
+A plain run does what the headline figure needs and nothing else: it sets up, ages the population,
+warms up, times one window of exactly K steps, writes the last step's outputs if `--dump-outputs`
+is given, and prints the line.  `--full` adds everything else the benchmark measures or checks
+(five windows with the median reported, the secondary figures -- reset info, eager API, generic
+kernel, other airframes, rollout, re-trim, out-of-cache --, the parity report, the CPU baseline
+and, with N > 1, BASELINE config 5: 1 048 576 envs sharded over the ranks, observations gathered to
+rank 0 over RCCL every step, with and without the gather).  `--gather-obs` makes config 5 the
+headline instead.
 """
 import argparse
 import json
@@ -46,6 +53,7 @@ HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md (spec; 6.3 TB/s measured copy)
 REFERENCE_NUMPY_PER_CORE = 1367.0   # env-steps/s/core, reference on config 1
 CONFIG5_TOTAL = 1048576             # BASELINE configs[4]
 OUT_OF_CACHE_ENVS = 4194304         # 1.32 GB moved per launch: past the 256 MB Infinity Cache
+DUMP_BYTES_MAX = 64 * 1000 * 1000   # --dump-outputs: all files together
 
 
 def parse():
@@ -53,7 +61,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000, help="steps per timed window (exactly)")
     ap.add_argument("--warmup", type=int, default=100)
-    ap.add_argument("--repeats", type=int, default=5, help="timed windows; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed windows, the median is reported (default: 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: five windows, the secondary "
+                         "figures, the parity report, the CPU baseline, with N > 1 BASELINE config 5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (obs, reward, "
+                         "terminated, truncated, info) and the env state after it as DIR/<name>.npy (float32)")
     ap.add_argument("--age-seconds", type=float, default=60.0,
                     help="simulated seconds every env population is stepped (untimed, after reset) before its "
                          "graphs are captured, so that timed windows see steady-state episode phases and resets")
@@ -84,7 +99,12 @@ def parse():
                     help="step with the generic kernel instead of the default airframe's constant-specialised one")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rank / timing plumbing only, no kernel (CPU tests); value is null")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:   # a plain run: the headline only
+        args.no_secondary = args.no_cpu_baseline = args.no_parity = True
+    return args
 
 
 # ------------------------------------------------------------------------------------ launcher
@@ -482,27 +502,66 @@ class TimedGraph:
         layout = int(os.environ.get("HG_TG_LAYOUT", "2"))
         W = self.W = 8 if layout == 2 else 0
         P = self.P = int(os.environ.get("HG_TG_PREROLL", str(max(B, 1000))))
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=s):
-            for k in range(P - W):
+        # a window of more than C steps is cut into graphs of at most C steps, replayed back to back on
+        # one stream (a graph of millions of kernel nodes would cost more to build than to run): the
+        # head holds the pre-roll, the first stamp and C steps, the tail the last steps and the second
+        # stamp, a graph of C steps is replayed in between.  The stamps still bracket exactly K steps;
+        # a graph boundary costs the GPU one graph-launch gap (graphs_for: about 8 us) per C steps
+        # (300 000 steps in 30 graphs: 6.79 us per step, as 10 000 steps in one).
+        C = max(B, int(os.environ.get("HG_TG_CHUNK", "10000")) // B * B)
+        head = min(K, C)
+        mid = (K - head - 1) // C if K > head else 0
+        tail = K - head - mid * C
+        self.chunks = (head, mid, tail)
+
+        def steps(k0, count_):
+            for k in range(k0, k0 + count_):
                 one_step(k % B)
+
+        def begin():
+            steps(0, P - W)
             if layout != 1:
                 count(0)
-            for k in range(P - W, P):
-                one_step(k % B)
+            steps(P - W, W)
             stamp(0)
-            for k in range(K):
-                one_step(k % B)
+            steps(0, head)
+
+        def end():
             stamp(1)
             if layout != 1:
                 count(1)
             else:
                 self.n = [self.stamps[0] * 0, self.stamps[0] * 0]
-        self()
+        self.graph = torch.cuda.CUDAGraph()
+        self.graphs = [(self.graph, 1)]
+        with torch.cuda.graph(self.graph, stream=s):
+            begin()
+            if tail == 0:
+                end()
+        if tail:
+            if mid:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, stream=s):
+                    steps(head, C)
+                self.graphs.append((g, mid))
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=s):
+                steps(head + mid * C, tail)
+                end()
+            self.graphs.append((g, 1))
+            # a cut window is long, a rehearsal of all of it would double the run: the head's pre-roll
+            # warms the head; the middle and tail graphs are replayed once each, untimed, so that their
+            # first launch (the upload of up to C kernel nodes) never falls between the stamps
+            for g, _ in self.graphs[1:]:
+                g.replay()
+        else:
+            self()
         torch.cuda.synchronize()
 
     def __call__(self):
-        self.graph.replay()
+        for g, times in self.graphs:
+            for _ in range(times):
+                g.replay()
 
     def inner_s(self):
         t = self.stamps.tolist()
@@ -519,8 +578,9 @@ def windows(torch, dev, one_step, K, B, env=None):
     if os.environ.get("HG_BENCH_OUTER_WINDOWS") != "1" and env is not None and hasattr(env, "lib"):
         try:
             tg = TimedGraph(torch, dev, one_step, K, B, env)
+            cut = (f", cut into graphs of at most {tg.chunks[0]} steps replayed back to back" if tg.chunks[2] else "")
             return tg, (tg,), (f"one hipGraph per window: {tg.P} pre-roll steps (the last {tg.W} after the first "
-                               f"episode count), then the {K} timed steps between two GPU clock stamps")
+                               f"episode count), then the {K} timed steps between two GPU clock stamps" + cut)
         except Exception as exc:   # (reported in the mode string)
             torch.cuda.synchronize()
             progress(f"TimedGraph unavailable ({exc}); graph replays")
@@ -629,6 +689,33 @@ def episodes(env, sync=True):
     _, c = env.get_state()
     n = c[:, 2].long().sum()
     return int(n.item()) if sync else n
+
+
+def dump_outputs(path, env, rank, world):
+    """--dump-outputs: what the last timed step returned to its caller (the env's obs, reward,
+    terminated, truncated and info buffers; nothing has stepped the env since) and the state after it
+    (get_state), as `path`/<name>.npy (rank r > 0: <name>_rank<r>.npy) in float32, the int32 counters
+    in float64.  The env, its noise and the action bank are seeded and the number of steps before the
+    last one follows from the arguments, so two runs with the same arguments dump the same step.  All
+    files of all ranks stay under DUMP_BYTES_MAX: of a larger population a fixed, seeded sample of
+    rows is written, its env indices as rows.npy."""
+    import numpy as np
+    env.torch.cuda.synchronize()
+    state, counters = env.get_state()
+    arrays = {"obs": (env.obs, np.float32), "reward": (env.reward, np.float32),
+              "terminated": (env.terminated_u8, np.float32), "truncated": (env.truncated_u8, np.float32),
+              "info": (env.info_u8, np.float32), "state": (state, np.float32), "counters": (counters, np.float64)}
+    host = {k: v.detach().cpu().numpy().astype(dt) for k, (v, dt) in arrays.items()}
+    per_row = sum(a.nbytes // env.num_envs for a in host.values()) + 8
+    keep = max(1, (DUMP_BYTES_MAX // max(1, world) - 4096) // per_row)
+    if keep < env.num_envs:
+        rows = np.sort(np.random.default_rng(0x5EED).choice(env.num_envs, size=keep, replace=False))
+        host = {k: a[rows] for k, a in host.items()}
+        host["rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + (f"_rank{rank}" if rank else "") + ".npy"), np.ascontiguousarray(a))
+    progress(f"dump-outputs: {len(host)} arrays of {min(keep, env.num_envs)} envs in {path}")
 
 
 def gather_loop(torch, dist, env, bank, B, K, rank, world, dev, backend, overlap=True):
@@ -858,6 +945,8 @@ def main():
         sys.exit(f"bench.py: process group has {seen_world} ranks, expected {world}")
     if args.gather_obs and world < 2:
         sys.exit("bench.py: --gather-obs needs N > 1 ranks")
+    if args.gather_obs and args.dump_outputs:
+        sys.exit("bench.py: --dump-outputs writes the sharded step's outputs, not --gather-obs's")
     if args.dry_run:
         from contextlib import nullcontext
         torch.cuda.Event = _HostEvent
@@ -928,6 +1017,8 @@ def main():
         sec, secs, wall, resets = timer.run_counted(env, replay, R)
         per_rank = timer.per_rank
         head_event_s = timer.event_s
+        if args.dump_outputs and not args.dry_run:
+            dump_outputs(args.dump_outputs, env, rank, world)
         if args.dry_run:
             mode = f"{K} eager launches (dry run)"
         total_envs = N * world
@@ -1104,6 +1195,7 @@ def main():
         "n_gpus": world,
         "steps": K,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": sec / K * 1e3,
         "higher_is_better": True,
         "scaling": "weak",

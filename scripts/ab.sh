@@ -7,7 +7,7 @@
 #             (scripts/build_variants.py NAME=-DFLAG=1,...)                          default "cur prev"
 #   ARGS      extra bench.py arguments (default: headline workload, 1 000-step windows, 3 repeats)
 #   FIELD     the bench-line value compared, a dotted path (ms_per_step, retrim.ms_per_step,
-#             out_of_cache.ms_per_step, ...)                                          default ms_per_step
+#             out_of_cache.ms_per_step, ...; a secondary figure needs --full in ARGS)  default ms_per_step
 #   ROUNDS    interleaved rounds                                                      default 3
 #   TAG       output name under gpurun_out/ (ab_<TAG>.jsonl, one bench line per run)  default ab
 #

@@ -56,6 +56,32 @@ def test_reference_airframe_file_and_terrain_png():
     np.testing.assert_array_equal(config.load_terrain(doc), config.load_terrain(ours))
 
 
+def test_reference_layout_file_and_terrain_png(tmp_path):
+    """A parameter file and a 16-bit heightmap PNG laid out as the reference lays them out (the
+    document's ENV.HMAP_PATH under a resource directory) load to the bundled values, the terrain
+    from the PNG itself.  Both files are written here from the bundled data, so this covers the
+    resource-directory and PNG paths of the loader wherever the suite runs; the comparison with
+    independent data is test_reference_airframe_file_and_terrain_png's."""
+    from PIL import Image
+    ours = config.load_airframe("aw109")
+    u16 = config.load_terrain(ours)
+    res = tmp_path / "resources"
+    png = res / "models" / "terrain" / "terrain_hmap.png"
+    png.parent.mkdir(parents=True)
+    Image.fromarray(u16).save(str(png))
+    p = tmp_path / "helis" / "aw109.yaml"
+    p.parent.mkdir()
+    p.write_text(yaml.safe_dump(_to_reference_schema(ours)))
+    doc = config.load_airframe(str(p), resource_dir=str(res))
+    assert doc["terrain"]["file"] == str(png)
+    assert set(doc["airframe"]) == set(ours["airframe"])
+    for k, v in ours["airframe"].items():
+        assert float(doc["airframe"][k]) == float(v), k
+    got = config.load_terrain(doc)
+    assert got.dtype == np.uint16 and got.shape == u16.shape
+    np.testing.assert_array_equal(got, u16)
+
+
 def test_missing_fields_are_reported(tmp_path):
     ref = _to_reference_schema(config.load_airframe("aw109"))
     del ref["HELI"]["MR"]["RPM"]

@@ -10,15 +10,31 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run(*args, env=None):
+def run(*args, env=None, full=True):
+    """bench.py --dry-run; full: with --full (config 5 and the other secondary figures are behind it)."""
     e = dict(os.environ)
     e.pop("WORLD_SIZE", None)
     e.update(env or {})
+    more = ["--full", "--repeats", "2"] if full else []
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "12",
-                        "--warmup", "2", "--repeats", "2", *args], capture_output=True, text=True, env=e,
+                        "--warmup", "2", *more, *args], capture_output=True, text=True, env=e,
                        timeout=300, cwd=ROOT)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     return p.returncode, lines, p.stderr
+
+
+def test_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full: one window of exactly --steps steps, ms_per_step, no secondary figure, and a
+    dry run (no kernel, no outputs) writes nothing for --dump-outputs."""
+    rc, lines, err = run("--gpus", "1", "--dump-outputs", str(tmp_path / "dump"), full=False)
+    assert rc == 0, err[-2000:]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 12 and d["warmup"] == 2 and d["timing"]["repeats"] == 1 and len(d["timing"]["window_s"]) == 1
+    assert d["ms_per_step"] == d["timing"]["median_window_s"] / 12 * 1e3
+    assert d["full"] is False and d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "fp32"
+    assert not [k for k in ("config5", "cpu_baseline", "max_abs_step_err", "rollout", "retrim") if k in d]
+    assert not (tmp_path / "dump").exists()
 
 
 def test_gpus_2_spawns_two_ranks_and_reports_config5():
