@@ -378,7 +378,16 @@ __device__ unsigned long long g_timing_help[HG_TIMING_WAVES][5];
 
 }  // namespace
 #include "stage_f32.h"   // (after the timing macros: HG_STAGE_STAMP)
+#include "policy_mlp.h"  // (after philox / u01)
 namespace {
+
+// hg_rollout_policy's arguments beside StepArgs (which keeps its size: the per-step kernels' argument
+// segment is three scalar-cache lines)
+struct PolicyArgs {
+    const float* pk = nullptr;     // the handle's packed policy (policy_mlp.h)
+    const float* obs0 = nullptr;   // [N,17] the observations step 0's actions are computed from
+    float* actions_out = nullptr;  // [nsteps,N,4] the sampled actions
+};
 
 // TASK: reward / success of the task; ETA: noise injected by the caller (else in-kernel Philox);
 // NT: streaming output stores (see st_out); FEAT: the optional features (reset-info compaction,
@@ -387,13 +396,19 @@ namespace {
 // kept in registers between them; BAKED: the default airframe's model constants compiled in as
 // instruction literals (baked.h), the runtime fields still read from the device copy.  All
 // compile-time, so the hot kernel has no data-independent branches to merge around.
+// POLICY (with MULTI: hg_rollout_policy): each step's action is the handle's MLP policy
+// (policy_mlp.h) of the observation row the previous step wrote -- the lane's `obs` registers, from
+// `pol.obs0` at the first step -- and is stored to pol.actions_out; a.actions is not read.
 // The body is a device function so that the run-time specialised code objects (step_rtc.hip) wrap
 // the same code in kernels of their own names.
-template <int TASK, bool ETA, bool NT, bool FEAT, bool MULTI, bool BAKED, bool NTS, int HELP = 0>
+template <int TASK, bool ETA, bool NT, bool FEAT, bool MULTI, bool BAKED, bool NTS, int HELP = 0, bool POLICY = false>
 __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p,
                                           ParamArg Pa, const Template<float>* __restrict__ Tp, const StepArgs& a,
-                                          int64_t bid) {
+                                          int64_t bid, const PolicyArgs& pol = PolicyArgs{}) {
     static_assert(HELP == 0 || (!ETA && !MULTI), "wind helper waves: in-kernel noise, one step per launch");
+    static_assert(!POLICY || (MULTI && HELP == 0), "the in-kernel policy belongs to the rollout");
+    // the policy's matrix products take the wave's 64 envs as their columns: a block is one wave
+    static_assert(!POLICY || kStepBlock == 64, "hg_rollout_policy needs one-wave step blocks (HG_STEP_BLOCK 64)");
     __shared__ float s_obs[(HELP ? HELP * 64 : kStepBlock) * HG_N_OBS];   // one 64-row slice per wave
     __shared__ float s_wind[HELP ? HELP * 8 * 64 : 1];   // HELP: each tile's wind output and wind state
     constexpr bool kNTS = NT || NTS;   // non-temporal output stores
@@ -543,12 +558,30 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
             }
         }
     };
+    // POLICY: the weights as this lane's matrix operands, kept across the steps, and the observation
+    // row the next action is computed from (lanes past the end of a ragged tile read row blk0)
+    hgp::Weights pw;
+    float pobs[POLICY ? 17 : 1];
+    if constexpr (POLICY) {
+        hgp::load_weights(pol.pk, lane, pw);
+        const float* row = pol.obs0 + (blk0 + lo) * 17;
+#pragma unroll
+        for (int c = 0; c < 17; ++c) pobs[c] = row[c];
+    }
     for (int sstep = 0; sstep < nsteps; ++sstep) {
     // MULTI: the constants are re-read (scalar cache) each step rather than kept live across the
     // loop, where ~130 of them would spill out of the SGPR file
     const Params<float>& P = BAKED ? PB : (MULTI ? *reload_params(Pa) : P0);
     const int64_t so = MULTI ? (int64_t)sstep * n : 0;   // first row of this step's inputs / outputs
-    const float4 act = ld_lane(reinterpret_cast<const float4*>(a.actions) + so + blk0, lo);
+    float4 act;
+    if constexpr (POLICY) {
+        act = hgp::policy_action(pw, pol.pk, pobs, lane, seed_p, (uint64_t)(envoff_p + blk0 + lo), step, epi);
+        if (active)
+            st_lane<kNTS>(reinterpret_cast<f32x4*>(pol.actions_out) + so + blk0, (uint32_t)tid,
+                          f32x4{act.x, act.y, act.z, act.w});
+    } else {
+        act = ld_lane(reinterpret_cast<const float4*>(a.actions) + so + blk0, lo);
+    }
     // terrain texels under the committed position (F6): issued now, combined after the wind step
     const hg::GroundCell<float> cell_c = hg::ground_cell(P, hs[15], hs[16]);
     const hg::GroundTexels tex_c = hg::ground_fetch(a.hmap, cell_c);
@@ -827,6 +860,10 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
     uint64_t skip_rows = 0;
     if (FEAT && !MULTI) skip_rows = __ballot(defer);
     store_obs_wave<kNTS, MULTI>(s_obs + wv * 64 * HG_N_OBS, obs, a.obs, so, blk0, n, lane, skip_rows);
+    if constexpr (POLICY) {
+#pragma unroll
+        for (int c = 0; c < 17; ++c) pobs[c] = obs[c];
+    }
     }   // steps
     TSTAMP(13, "v"(hs[0]), "v"(carry[3]));
     st_b = reinterpret_cast<f32x4*>(state_p + tile * kTileWords) + 4 * kTileEnvs;
@@ -902,6 +939,21 @@ __global__ __launch_bounds__(128 * HG_HELPER, 1) void step_help_kernel(float* __
 #endif
 
 #ifndef HG_RTC
+// hg_rollout_policy: the rollout with the handle's MLP policy evaluated in the kernel.  One wave per
+// block and at most one wave per SIMD, deliberately: the policy's matrix operands (117 registers per
+// lane, policy_mlp.h) stay in registers across the steps beside the two layers' accumulators (128)
+// and the step's own registers, which needs the whole 512-register file of a SIMD; the matrix pipe
+// is busy from one wave (four independent accumulator tiles).  More envs than one wave per SIMD run
+// as further rounds of blocks.  The step is the lone-wave (NT) variant.
+template <int TASK, bool ETA, bool FEAT, bool BAKED>
+__global__ __launch_bounds__(64, 1) void rollout_policy_kernel(float* __restrict__ state_p, int64_t n_p, uint64_t seed_p,
+                                                               int64_t envoff_p, ParamArg Pa,
+                                                               const Template<float>* __restrict__ Tp, const StepArgs a,
+                                                               const PolicyArgs pol) {
+    step_body<TASK, ETA, true, FEAT, true, BAKED, false, 0, true>(state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x,
+                                                                  pol);
+}
+
 // reset_mode RETRIM with next-step auto-reset (hg_env::ov): one launch holds the trims of the previous
 // step's ends -- its first `tb` blocks, one wave per trim (retrim_body.h) -- and this step, whose
 // deferred resets store only their step counter while those trims write the rest.  Both parts fit
@@ -1162,6 +1214,62 @@ __global__ __launch_bounds__(kBlock) void eta_kernel(const float* state, int64_t
     out[3 * i + 0] = eta[0];
     out[3 * i + 1] = eta[1];
     out[3 * i + 2] = eta[2];
+}
+
+// hg_set_policy: the caller's weights into the handle's packed image, each matrix element where the
+// lane that uses it as a matrix operand loads it from (layout: policy_mlp.h)
+__global__ __launch_bounds__(kBlock) void policy_pack_kernel(const float* W1, const float* b1, const float* W2,
+                                                             const float* b2, const float* W3, const float* b3,
+                                                             const float* log_std, const float* obs_mean,
+                                                             const float* obs_scale, float* pk) {
+    const int idx = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (idx >= hgp::kPolicyFloats) return;
+    float v = 0.f;
+    if (idx < hgp::kHeadFloats) {
+        if (idx < hgp::kStdOff + 4) v = log_std ? expf(log_std[idx - hgp::kStdOff]) : 0.f;
+        else if (idx == hgp::kStochOff) v = log_std ? 1.f : 0.f;
+        else if (idx >= hgp::kMeanOff && idx < hgp::kMeanOff + 17) v = obs_mean ? obs_mean[idx - hgp::kMeanOff] : 0.f;
+        else if (idx >= hgp::kScaleOff && idx < hgp::kScaleOff + 17) v = obs_scale ? obs_scale[idx - hgp::kScaleOff] : 1.f;
+    } else {
+        const int s = (idx - hgp::kHeadFloats) >> 6, l = (idx - hgp::kHeadFloats) & 63;
+        const int h = l >> 5, i = l & 31;
+        if (s < hgp::kL1Slots) {
+            const int mt = s / hgp::kL1Steps, k = 2 * (s % hgp::kL1Steps) + h, row = 32 * mt + i;
+            v = k < 17 ? W1[row * 17 + k] : b1[row];
+        } else if (s < hgp::kL1Slots + hgp::kL2Slots) {
+            const int s2 = s - hgp::kL1Slots, mt = s2 / hgp::kL2Steps, kp = s2 % hgp::kL2Steps, row = 32 * mt + i;
+            if (kp < 32) v = W2[row * 64 + hgp::acc_row(kp >> 4, kp & 15, h)];
+            else v = h == 0 ? b2[row] : 0.f;
+        } else if (i < 8) {
+            const int kp = s - hgp::kL1Slots - hgp::kL2Slots, o = i & 3;
+            if (kp < 32) v = W3[o * 64 + hgp::acc_row(kp >> 4, kp & 15, h)];
+            else v = h == 0 ? b3[o] : 0.f;
+        }
+    }
+    pk[idx] = v;
+}
+
+// hg_policy_act: one wave per state tile computes its envs' actions from the given observation rows
+// and the envs' counters in the tile (the noise key, as eta_kernel reads them) with the function the
+// rollout calls; the env is not modified.  Lanes past the end of a ragged tile compute on row
+// 64 * tile and store nothing.
+__global__ __launch_bounds__(64, 1) void policy_act_kernel(const float* __restrict__ state, int64_t n, uint64_t seed,
+                                                           int64_t env_offset, const float* __restrict__ pk,
+                                                           const float* __restrict__ obs, float* actions) {
+    const int lane = threadIdx.x;
+    const int64_t blk0 = (int64_t)blockIdx.x * 64;
+    const bool active = blk0 + lane < n;
+    const uint32_t lo = (uint32_t)(active ? lane : 0);
+    const int64_t i = blk0 + lo;
+    hgp::Weights pw;
+    hgp::load_weights(pk, lane, pw);
+    const int32_t* ctr = reinterpret_cast<const int32_t*>(state);
+    const int32_t step = ctr[tix(i, kCtrCol0 + 0)], epi = ctr[tix(i, kCtrCol0 + 2)];
+    float o[17];
+#pragma unroll
+    for (int c = 0; c < 17; ++c) o[c] = obs[i * 17 + c];
+    const float4 a = hgp::policy_action(pw, pk, o, lane, seed, (uint64_t)(env_offset + i), step, epi);
+    if (active) reinterpret_cast<float4*>(actions)[i] = a;
 }
 
 // hg_debug_philox: the device Philox4x32-10 on given counters and keys, rows {c0, c1, c2, c3, k0, k1}
@@ -1518,6 +1626,8 @@ struct hg_env {
     int32_t* ov_ring = nullptr;             // [3] their counts
     float* tmpl_env = nullptr;              // per-env reset templates [N][39] (hg_set_reset_templates)
     bool env_templates = false;
+    float* policy_dev = nullptr;            // the MLP policy's packed image (hg_set_policy, policy_mlp.h)
+    bool policy_set = false;
     bool baked = false;                     // step with the constant-specialised kernel (baked.h)
     bool baked_allowed = true;              // ... unless switched off (hg_set_specialized)
     // a run-time specialised code object for another airframe (step_rtc.hip, hg_load_specialized)
@@ -1717,6 +1827,31 @@ static hipError_t dispatch_task(const hg_env* e, hipStream_t s, const StepArgs& 
     }
 }
 
+// hg_rollout_policy's launch: task x injected noise x optional features, the constant-specialised
+// step when the env uses it
+template <int T>
+static void launch_rollout_policy(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol, bool eta,
+                                  bool feat) {
+    const unsigned grid = (unsigned)((e->n + 63) / 64);
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, STEP_KARGS(e), a, pol); };
+    ++e->n_launch[4];
+    if (e->baked) {
+        if (feat) eta ? go(rollout_policy_kernel<T, true, true, true>) : go(rollout_policy_kernel<T, false, true, true>);
+        else eta ? go(rollout_policy_kernel<T, true, false, true>) : go(rollout_policy_kernel<T, false, false, true>);
+    } else {
+        if (feat) eta ? go(rollout_policy_kernel<T, true, true, false>) : go(rollout_policy_kernel<T, false, true, false>);
+        else eta ? go(rollout_policy_kernel<T, true, false, false>) : go(rollout_policy_kernel<T, false, false, false>);
+    }
+}
+static void dispatch_rollout_policy(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol, bool eta,
+                                    bool feat) {
+    switch (e->cfg.task) {
+        case HG_TASK_HOVER: launch_rollout_policy<HG_TASK_HOVER>(e, s, a, pol, eta, feat); break;
+        case HG_TASK_FORWARD_FLIGHT: launch_rollout_policy<HG_TASK_FORWARD_FLIGHT>(e, s, a, pol, eta, feat); break;
+        default: launch_rollout_policy<HG_TASK_HELI>(e, s, a, pol, eta, feat); break;
+    }
+}
+
 // ov mode's launch: `ov_trim_blocks` trim blocks (the previous step's ends; blocks without a job exit at
 // once) ahead of the step's blocks -- never more than one per env (a step ends at most n episodes)
 #ifndef HG_OV_TB_DIV   // (A/B knob: the overlapped launch's trim blocks, n / 256 / this)
@@ -1865,7 +2000,7 @@ static void release(hg_env* e) {
     dfree(e->hmap); dfree(e->state); dfree(e->az); dfree(e->tmpl_dev); dfree(e->params_dev);
     dfree(e->trim_block); dfree(e->retrim_wind); dfree(e->retrim_list); dfree(e->retrim_recs);
     dfree(e->ov_recs); dfree(e->ov_ring); dfree(e->fused_ring);
-    dfree(e->tmpl_env); dfree(e->setup_batch);
+    dfree(e->tmpl_env); dfree(e->setup_batch); dfree(e->policy_dev);
     delete e;
 }
 
@@ -1966,6 +2101,10 @@ int32_t hg_create(const hg_config* cfg, const double* terrain_ft, int32_t rows, 
         return cleanup(err, "hipMemcpy params64");
     if ((err = hipMalloc(&e->fused_ring, 3 * kFusedSlot * sizeof(int32_t))) != hipSuccess) return cleanup(err, "hipMalloc fused ring");
     if ((err = hipMemset(e->fused_ring, 0, 3 * kFusedSlot * sizeof(int32_t))) != hipSuccess) return cleanup(err, "hipMemset fused ring");
+    if ((err = hipMalloc(&e->policy_dev, sizeof(float) * hgp::kPolicyFloats)) != hipSuccess)
+        return cleanup(err, "hipMalloc policy");
+    if ((err = hipMemset(e->policy_dev, 0, sizeof(float) * hgp::kPolicyFloats)) != hipSuccess)
+        return cleanup(err, "hipMemset policy");
     if (cfg->reset_mode == HG_RESET_RETRIM) {
         if ((err = hipMalloc(&e->retrim_wind, sizeof(float) * 3 * num_envs)) != hipSuccess)
             return cleanup(err, "hipMalloc retrim wind");
@@ -2343,6 +2482,75 @@ int32_t hg_rollout(hg_env* e, const float* actions, int32_t nsteps, float* obs, 
     const bool feat = e->Pf.autoreset_next || e->Pf.max_episode_steps != INT32_MAX || e->Pf.env_templates ||
                       e->Pf.reset_retrim;
     HIP_TRY(dispatch_task<true>(e, s, a, eta != nullptr, feat));
+    HIP_TRY(hipGetLastError());
+    return HG_OK;
+}
+
+int32_t hg_set_policy(hg_env* e, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
+                      const float* b3, const float* log_std, const float* obs_mean, const float* obs_scale,
+                      void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3)
+        return fail(HG_E_INVALID, "hg_set_policy: W1/b1/W2/b2/W3/b3 must be device pointers");
+    e->ov_chain = kChainBroken;   // the next step's pending resets take the serial re-trim
+    e->chain_expect = kChainBroken;
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    hipLaunchKernelGGL(policy_pack_kernel, dim3(grid_for(hgp::kPolicyFloats)), dim3(kBlock), 0, (hipStream_t)stream, W1, b1,
+                       W2, b2, W3, b3, log_std, obs_mean, obs_scale, e->policy_dev);
+    HIP_TRY(hipGetLastError());
+    e->policy_set = true;
+    return HG_OK;
+}
+
+int32_t hg_policy_act(hg_env* e, const float* obs, float* actions, void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!e->policy_set) return fail(HG_E_INVALID, "hg_policy_act: no policy set (hg_set_policy)");
+    if (!obs || !actions) return fail(HG_E_INVALID, "hg_policy_act: obs/actions must be device pointers");
+    if ((uintptr_t)actions & 15) return fail(HG_E_INVALID, "actions must be 16-byte aligned");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    hipLaunchKernelGGL(policy_act_kernel, dim3((unsigned)((e->n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, e->state,
+                       (int64_t)e->n, (uint64_t)e->cfg.seed, (int64_t)e->cfg.env_offset, e->policy_dev, obs, actions);
+    HIP_TRY(hipGetLastError());
+    return HG_OK;
+}
+
+int32_t hg_rollout_policy(hg_env* e, const float* obs0, int32_t nsteps, float* actions_out, float* obs, float* reward,
+                          uint8_t* terminated, uint8_t* truncated, uint8_t* info, const float* eta, void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!e->policy_set) return fail(HG_E_INVALID, "hg_rollout_policy: no policy set (hg_set_policy)");
+    if (nsteps < 1) return fail(HG_E_INVALID, "nsteps must be >= 1");
+    if (!obs0 || !actions_out || !obs || !reward || !terminated || !truncated)
+        return fail(HG_E_INVALID, "obs0/actions_out/obs/reward/terminated/truncated must be device pointers");
+    if (((uintptr_t)actions_out & 15) || ((uintptr_t)obs & 15))
+        return fail(HG_E_INVALID, "actions_out and obs must be 16-byte aligned");
+    if (e->Pf.reset_retrim && e->Pf.autoreset)
+        return fail(HG_E_INVALID, "hg_rollout_policy does not support auto-resets in reset_mode RETRIM (re-trims run between steps)");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    e->ov_chain = kChainBroken;   // the next step's pending resets take the serial re-trim
+    e->chain_expect = kChainBroken;
+    StepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.hmap = e->hmap;
+    a.obs = obs;
+    a.reward = reward;
+    a.terminated = terminated;
+    a.truncated = truncated;
+    a.info = info;
+    a.eta = eta;
+    a.tmpl_env = e->tmpl_env;
+    a.nsteps = nsteps;
+    a.retrim_slot = -1;
+    a.retrim_wind = e->retrim_wind;   // (reset_mode RETRIM without auto-reset: as hg_rollout)
+    PolicyArgs pol;
+    pol.pk = e->policy_dev;
+    pol.obs0 = obs0;
+    pol.actions_out = actions_out;
+    const bool feat = e->Pf.autoreset_next || e->Pf.max_episode_steps != INT32_MAX || e->Pf.env_templates ||
+                      e->Pf.reset_retrim;
+    dispatch_rollout_policy(e, (hipStream_t)stream, a, pol, eta != nullptr, feat);
     HIP_TRY(hipGetLastError());
     return HG_OK;
 }

@@ -103,6 +103,9 @@ _SIGS = {
     "hg_random_actions": (ctypes.c_int32, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_float,
                                            ctypes.c_float, _P]),
     "hg_rollout": (ctypes.c_int32, [_P, _P, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "hg_set_policy": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "hg_policy_act": (ctypes.c_int32, [_P, _P, _P, _P]),
+    "hg_rollout_policy": (ctypes.c_int32, [_P, _P, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hg_trim_batch": (ctypes.c_int32, [_P, _P, ctypes.c_int64, _P, _P, _P, _P, _P]),
     "hg_retrim_failures": (ctypes.c_int32, [_P, ctypes.POINTER(ctypes.c_int64)]),
     "hg_set_retrim_overlap": (ctypes.c_int32, [_P, ctypes.c_int32]),

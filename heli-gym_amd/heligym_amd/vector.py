@@ -537,6 +537,75 @@ class HeliVecEnv(*_VEC_BASES):
                                         _ptr(info), _ptr(e), self._stream()))
         return out
 
+    # ------------------------------------------------------------------ closed-loop policy rollouts
+    def set_policy(self, model_or_pairs, log_std=None, obs_mean=None, obs_scale=None):
+        """Give the env its MLP policy (hg_set_policy): three (W, b) pairs or an nn.Sequential of
+        Linear(17, 64) / Tanh / Linear(64, 64) / Tanh / Linear(64, 4), fp32 (heligym_amd.policy).
+        log_std [4]: the action noise's log standard deviation, None for a deterministic policy;
+        obs_mean / obs_scale [17]: the input normalisation x = (obs - obs_mean) * obs_scale.
+        The weights are copied into the handle's own buffer on the current stream (no allocation, no
+        sync, capturable): call it again after every update of the model."""
+        from . import policy
+        t = self.torch
+        packed = policy.pack_policy(model_or_pairs, log_std, obs_mean, obs_scale)
+        dev = tuple(None if p is None else p.to(device=self.device, dtype=t.float32).contiguous() for p in packed)
+        self._keep_policy = dev
+        self._check(self.lib.hg_set_policy(self._h, *(_ptr(p) for p in dev), self._stream()))
+
+    def _obs_arg(self, obs, name):
+        if obs is None:
+            return self.obs
+        t = self.torch
+        if (obs.dtype != t.float32 or obs.device != self.device or not obs.is_contiguous()
+                or tuple(obs.shape) != (self.num_envs, _abi.HG_N_OBS)):
+            raise ValueError(f"{name} must be a contiguous float32 [{self.num_envs}, 17] tensor on {self.device}, "
+                             f"got {tuple(obs.shape)} {obs.dtype} on {obs.device}")
+        return obs
+
+    def policy_act(self, obs=None, out=None):
+        """The policy's actions [N,4] for the observations `obs` [N,17] (default: `self.obs`) with the
+        noise of each env's current counters (hg_policy_act); the env is not modified.  policy_act then
+        step(), repeated, is bitwise rollout_policy()."""
+        t = self.torch
+        o = self._obs_arg(obs, "obs")
+        if out is None:
+            out = t.empty(self._act_shape, dtype=t.float32, device=self.device)
+        elif (tuple(out.shape) != self._act_shape or out.dtype != t.float32 or out.device != self.device
+              or not out.is_contiguous()):
+            raise ValueError(f"policy_act: out must be a contiguous float32 {self._act_shape} tensor on {self.device}")
+        self._check(self.lib.hg_policy_act(self._h, _ptr(o), _ptr(out), self._stream()))
+        return out
+
+    def rollout_policy(self, K, obs0=None, eta=None, out=None):
+        """Closed-loop rollout (hg_rollout_policy): K steps in one launch, each step's action computed
+        in the kernel by the env's policy (set_policy) from the observation the previous step wrote,
+        the first from `obs0` [N,17] (default: `self.obs`).  Returns (actions [K,N,4], obs [K,N,17],
+        reward [K,N], terminated, truncated, info bits [K,N] uint8) device tensors (`out` buffers are
+        reused if given, as returned by a previous call); `self.obs` is not written, so pass
+        `obs[-1]` as the next call's obs0.  The action noise is keyed by each env's global id and its
+        own counters, so sharding the envs over several HeliVecEnv (env_offset) changes nothing
+        (ShardedHeliVecEnv itself does not expose the policy calls)."""
+        t = self.torch
+        K, N = int(K), self.num_envs
+        o0 = self._obs_arg(obs0, "obs0")
+        e = None
+        if eta is not None:
+            e = eta.to(device=self.device, dtype=t.float32).contiguous()
+            if tuple(e.shape) != (K, N, 3):
+                raise ValueError("eta must be [K, N, 3]")
+        if out is None or out[0].shape[0] != K:
+            out = (t.empty((K, N, _abi.HG_N_ACT), dtype=t.float32, device=self.device),
+                   t.empty((K, N, _abi.HG_N_OBS), dtype=t.float32, device=self.device),
+                   t.empty((K, N), dtype=t.float32, device=self.device),
+                   t.empty((K, N), dtype=t.uint8, device=self.device),
+                   t.empty((K, N), dtype=t.uint8, device=self.device),
+                   t.empty((K, N), dtype=t.uint8, device=self.device))
+        act, obs, rew, term, trunc, info = out
+        self._keep = (o0, e)
+        self._check(self.lib.hg_rollout_policy(self._h, _ptr(o0), K, _ptr(act), _ptr(obs), _ptr(rew), _ptr(term),
+                                               _ptr(trunc), _ptr(info), _ptr(e), self._stream()))
+        return out
+
     def trim_batch(self, wind_ned):
         """Device batched trim (hg_trim_batch) of this env's trim condition against each row of
         `wind_ned` [K,3] (ft/s NED): the reset the reference computes from its second episode on.

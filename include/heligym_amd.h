@@ -254,6 +254,58 @@ int32_t hg_rollout(hg_env* env, const float* actions_dev, int32_t nsteps, float*
                    uint8_t* terminated_dev, uint8_t* truncated_dev, uint8_t* info_dev, const float* eta_dev,
                    void* stream);
 
+/* ---- Closed-loop rollouts: an MLP policy held by the handle and evaluated inside the rollout kernel.
+ *
+ * Model (fixed):   x = (obs - obs_mean) * obs_scale                               [17]
+ *                  a = W3 tanh(W2 tanh(W1 x + b1) + b2) + b3 + exp(log_std) * z     [4]
+ * W1 [64,17], b1 [64], W2 [64,64], b2 [64], W3 [4,64], b3 [4], row-major [out,in] as torch.nn.Linear
+ * stores them; log_std [4], obs_mean [17], obs_scale [17]; all fp32.  Two hidden layers of width 64
+ * with tanh, no other size or activation.  The action is the raw sampled value: it is not clipped
+ * (the reference does not clip actions either).
+ * Arithmetic: fp32 throughout.  Each matrix product is an fp32 fused-multiply-add chain (the exact
+ * fp32 matrix instruction, one rounding per product, the bias added last); tanh(v) = sign(v) (1 - t) /
+ * (1 + t) with t = exp2(-2 log2(e) |v|); x is one subtraction and one multiplication; the noise is
+ * added as fma(exp(log_std), z, mean action).  Against an fp64 evaluation of the same weights the
+ * error is that of an fp32 evaluation in another summation order.
+ * Noise: absent when log_std is NULL (deterministic policy: nothing is drawn).  Otherwise z is four
+ * standard normals from ONE Philox4x32-10 call and Box-Muller, by the device functions of the
+ * turbulence noise (hg_debug_eta):
+ *   counter = (gid_lo, gid_hi, episode step, episode index), gid = env_offset + i, the env's raw
+ *             counters (the step counter of an env waiting for its next-step reset is negative),
+ *             exactly the turbulence noise's counter;
+ *   key     = (seed_lo ^ 0x706F6C69, seed_hi ^ 0x63795F7A)  -- the turbulence key is (seed_lo, seed_hi),
+ *             so these two constants separate the streams;
+ *   words (r0, r1, r2, r3) -> u(r) = ((r >> 8) + 0.5) 2^-24 in fp32 (in (0, 1]), turn fraction
+ *             f(r) = (r >> 9) 2^-23;   R0 = sqrt(-2 ln u(r0)), R1 = sqrt(-2 ln u(r2));
+ *             z = (R0 cos 2 pi f(r1), R0 sin 2 pi f(r1), R1 cos 2 pi f(r3), R1 sin 2 pi f(r3)).
+ * The noise depends on the env's own counters only: it is the same however the envs are sharded
+ * over handles (env_offset), and the same in hg_rollout_policy and hg_policy_act.
+ *
+ * hg_set_policy: copy (repack) the weights into the handle's own device buffer, allocated by
+ * hg_create.  All arguments are device pointers; log_std, obs_mean, obs_scale may be NULL (no noise /
+ * 0 / 1).  Asynchronous on `stream`, allocates nothing, capturable into a graph: a training loop
+ * calls it once per update.  Like hg_rollout it ends a sequence of chained steps. */
+int32_t hg_set_policy(hg_env* env, const float* W1_dev, const float* b1_dev, const float* W2_dev,
+                      const float* b2_dev, const float* W3_dev, const float* b3_dev, const float* log_std_dev,
+                      const float* obs_mean_dev, const float* obs_scale_dev, void* stream);
+
+/* One action per env, actions_dev [N,4] (16-byte aligned), of the policy applied to obs_dev [N,17]
+ * with the noise of each env's current counters (read from the env's state as hg_debug_eta reads
+ * them).  The env is not modified.  The same device function as hg_rollout_policy's: acting and
+ * stepping (hg_step) in turn is bitwise that rollout.  HG_E_INVALID if no policy was set. */
+int32_t hg_policy_act(hg_env* env, const float* obs_dev, float* actions_dev, void* stream);
+
+/* hg_rollout with the actions computed in the kernel: step 0's from obs0_dev [N,17], step s+1's from
+ * the observation row step s writes (for an env auto-reset in step s that is its reset observation,
+ * per-env templates included).  The sampled actions go to actions_out_dev [nsteps,N,4]; the other
+ * outputs are stacked exactly as hg_rollout's.  Same restrictions and argument checks as hg_rollout
+ * (no auto-resets in HG_RESET_RETRIM; actions_out_dev and obs_dev 16-byte aligned); HG_E_INVALID if no
+ * policy was set.  One wave per SIMD (the weights stay in registers across the steps); counted by
+ * hg_debug_launches as a lone-wave launch, like hg_rollout's. */
+int32_t hg_rollout_policy(hg_env* env, const float* obs0_dev, int32_t nsteps, float* actions_out_dev,
+                          float* obs_dev, float* reward_dev, uint8_t* terminated_dev, uint8_t* truncated_dev,
+                          uint8_t* info_dev, const float* eta_dev, void* stream);
+
 /* Batched device trim: HelicopterDynamics.trim (helicopter_dynamics.py:491-576) of the env's trim
  * condition against `count` winds at once — the reset path of reset_mode HG_RESET_RETRIM, exposed
  * for direct use.  Same Newton iteration as hg_trim (fp64, trial point rounded to fp32), with the
