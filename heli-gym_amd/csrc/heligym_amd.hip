@@ -389,6 +389,14 @@ struct PolicyArgs {
     float* actions_out = nullptr;  // [nsteps,N,4] the sampled actions
 };
 
+// hg_rollout_ac's further outputs, [nsteps,N] each, any of them null (value and next_value together).
+// A struct of its own: PolicyArgs is a kernel argument of hg_rollout_policy's kernels.
+struct AcArgs {
+    float* logp = nullptr;         // log pi(a_k | o_k)
+    float* value = nullptr;        // V(o_k), o_k the observation a_k was computed from
+    float* next_value = nullptr;   // terminated[k] ? 0 : V(o'_k), o'_k step k's observation before any reset
+};
+
 // TASK: reward / success of the task; ETA: noise injected by the caller (else in-kernel Philox);
 // NT: streaming output stores (see st_out); FEAT: the optional features (reset-info compaction,
 // per-reset re-trim, next-step auto-reset, TimeLimit) -- without them the kernel carries none of
@@ -401,12 +409,20 @@ struct PolicyArgs {
 // `pol.obs0` at the first step -- and is stored to pol.actions_out; a.actions is not read.
 // The body is a device function so that the run-time specialised code objects (step_rtc.hip) wrap
 // the same code in kernels of their own names.
-template <int TASK, bool ETA, bool NT, bool FEAT, bool MULTI, bool BAKED, bool NTS, int HELP = 0, bool POLICY = false>
+// AC (with POLICY: hg_rollout_ac): the policy is evaluated by hgp::policy_eval, which also gives the
+// action's log-probability and the value head's V of the same observation, stored to ac.logp and
+// ac.value.  ac.next_value[k] is the value of the observation step k produced before any reset: where
+// step k did not reset, that is the next iteration's V, stored one step late (the last step's by one
+// more forward pass after the steps); where it reset, the terminal observation is about to be
+// overwritten and is evaluated at once, in a wave-uniform branch only waves with such a lane take.
+template <int TASK, bool ETA, bool NT, bool FEAT, bool MULTI, bool BAKED, bool NTS, int HELP = 0, bool POLICY = false,
+          bool AC = false>
 __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p,
                                           ParamArg Pa, const Template<float>* __restrict__ Tp, const StepArgs& a,
-                                          int64_t bid, const PolicyArgs& pol = PolicyArgs{}) {
+                                          int64_t bid, const PolicyArgs& pol = PolicyArgs{}, const AcArgs& ac = AcArgs{}) {
     static_assert(HELP == 0 || (!ETA && !MULTI), "wind helper waves: in-kernel noise, one step per launch");
     static_assert(!POLICY || (MULTI && HELP == 0), "the in-kernel policy belongs to the rollout");
+    static_assert(!AC || POLICY, "log-probabilities and values are the in-kernel policy's");
     // the policy's matrix products take the wave's 64 envs as their columns: a block is one wave
     static_assert(!POLICY || kStepBlock == 64, "hg_rollout_policy needs one-wave step blocks (HG_STEP_BLOCK 64)");
     __shared__ float s_obs[(HELP ? HELP * 64 : kStepBlock) * HG_N_OBS];   // one 64-row slice per wave
@@ -568,13 +584,31 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
 #pragma unroll
         for (int c = 0; c < 17; ++c) pobs[c] = row[c];
     }
-    for (int sstep = 0; sstep < nsteps; ++sstep) {
+    // AC: whether the previous step reset the lane (its next_value is stored already) or terminated it
+    bool ac_prev_reset = false, ac_prev_term = false;
+    // (AC with values: one more pass after the last step, which only evaluates the last observation)
+    const int niter = AC ? nsteps + (ac.next_value ? 1 : 0) : nsteps;
+    for (int sstep = 0; sstep < niter; ++sstep) {
     // MULTI: the constants are re-read (scalar cache) each step rather than kept live across the
     // loop, where ~130 of them would spill out of the SGPR file
     const Params<float>& P = BAKED ? PB : (MULTI ? *reload_params(Pa) : P0);
     const int64_t so = MULTI ? (int64_t)sstep * n : 0;   // first row of this step's inputs / outputs
     float4 act;
-    if constexpr (POLICY) {
+    if constexpr (AC) {
+        const hgp::Eval ev = hgp::policy_eval(pw, pol.pk, pobs, lane, seed_p, (uint64_t)(envoff_p + blk0 + lo), step, epi,
+                                              sstep < nsteps);
+        // the previous step's next_value where that step did not reset: this observation's value
+        if (ac.next_value && sstep > 0 && active && !ac_prev_reset)
+            st_lane<kNTS>(ac.next_value + (so - n) + blk0, (uint32_t)tid, ac_prev_term ? 0.f : ev.v);
+        if (sstep == nsteps) break;
+        act = ev.a;
+        if (active) {
+            st_lane<kNTS>(reinterpret_cast<f32x4*>(pol.actions_out) + so + blk0, (uint32_t)tid,
+                          f32x4{act.x, act.y, act.z, act.w});
+            if (ac.logp) st_lane<kNTS>(ac.logp + so + blk0, (uint32_t)tid, ev.logp);
+            if (ac.value) st_lane<kNTS>(ac.value + so + blk0, (uint32_t)tid, ev.v);
+        }
+    } else if constexpr (POLICY) {
         act = hgp::policy_action(pw, pol.pk, pobs, lane, seed_p, (uint64_t)(envoff_p + blk0 + lo), step, epi);
         if (active)
             st_lane<kNTS>(reinterpret_cast<f32x4*>(pol.actions_out) + so + blk0, (uint32_t)tid,
@@ -718,6 +752,23 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
 #pragma unroll
             for (int q = 0; q < 4; ++q) row[q] = f4u{obs[4 * q], obs[4 * q + 1], obs[4 * q + 2], obs[4 * q + 3]};
             a.final_obs_rows[i * 17 + 16] = obs[16];
+        }
+    }
+
+    if constexpr (AC) {
+        // next_value of a lane this step resets: V of its terminal observation (`obs`, before the reset
+        // below overwrites it), 0 where it terminated.  The forward pass runs only in waves with a lane
+        // that was truncated and reset, and then in all 64 lanes: the matrix instructions take every
+        // column, and a column's result depends on that column alone.
+        if (ac.next_value) {
+            if (__any(do_reset)) {
+                float vt = 0.f;
+                if (__any(do_reset && !term))
+                    vt = hgp::policy_eval(pw, pol.pk, obs, lane, seed_p, 0, 0, 0, false).v;
+                if (do_reset) st_lane<kNTS>(ac.next_value + so + blk0, (uint32_t)tid, term ? 0.f : vt);
+            }
+            ac_prev_reset = do_reset;
+            ac_prev_term = term;
         }
     }
 
@@ -952,6 +1003,18 @@ __global__ __launch_bounds__(64, 1) void rollout_policy_kernel(float* __restrict
                                                                const PolicyArgs pol) {
     step_body<TASK, ETA, true, FEAT, true, BAKED, false, 0, true>(state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x,
                                                                   pol);
+}
+
+// hg_rollout_ac: rollout_policy_kernel with the log-probabilities and the value head's values (step_body's
+// AC).  Same launch bound for the same reason; the terminal observation's forward pass is a second
+// inlined copy of the policy, which the register file holds without scratch.
+template <int TASK, bool ETA, bool FEAT, bool BAKED>
+__global__ __launch_bounds__(64, 1) void rollout_ac_kernel(float* __restrict__ state_p, int64_t n_p, uint64_t seed_p,
+                                                           int64_t envoff_p, ParamArg Pa,
+                                                           const Template<float>* __restrict__ Tp, const StepArgs a,
+                                                           const PolicyArgs pol, const AcArgs ac) {
+    step_body<TASK, ETA, true, FEAT, true, BAKED, false, 0, true, true>(state_p, n_p, seed_p, envoff_p, Pa, Tp, a,
+                                                                        blockIdx.x, pol, ac);
 }
 
 // reset_mode RETRIM with next-step auto-reset (hg_env::ov): one launch holds the trims of the previous
@@ -1217,7 +1280,8 @@ __global__ __launch_bounds__(kBlock) void eta_kernel(const float* state, int64_t
 }
 
 // hg_set_policy: the caller's weights into the handle's packed image, each matrix element where the
-// lane that uses it as a matrix operand loads it from (layout: policy_mlp.h)
+// lane that uses it as a matrix operand loads it from (layout: policy_mlp.h).  The value head's
+// elements are not written (value_pack_kernel's), so a head set before or after stays.
 __global__ __launch_bounds__(kBlock) void policy_pack_kernel(const float* W1, const float* b1, const float* W2,
                                                              const float* b2, const float* W3, const float* b3,
                                                              const float* log_std, const float* obs_mean,
@@ -1228,6 +1292,7 @@ __global__ __launch_bounds__(kBlock) void policy_pack_kernel(const float* W1, co
     if (idx < hgp::kHeadFloats) {
         if (idx < hgp::kStdOff + 4) v = log_std ? expf(log_std[idx - hgp::kStdOff]) : 0.f;
         else if (idx == hgp::kStochOff) v = log_std ? 1.f : 0.f;
+        else if (idx == hgp::kLogStdSumOff) v = log_std ? ((log_std[0] + log_std[1]) + log_std[2]) + log_std[3] : 0.f;
         else if (idx >= hgp::kMeanOff && idx < hgp::kMeanOff + 17) v = obs_mean ? obs_mean[idx - hgp::kMeanOff] : 0.f;
         else if (idx >= hgp::kScaleOff && idx < hgp::kScaleOff + 17) v = obs_scale ? obs_scale[idx - hgp::kScaleOff] : 1.f;
     } else {
@@ -1244,9 +1309,24 @@ __global__ __launch_bounds__(kBlock) void policy_pack_kernel(const float* W1, co
             const int kp = s - hgp::kL1Slots - hgp::kL2Slots, o = i & 3;
             if (kp < 32) v = W3[o * 64 + hgp::acc_row(kp >> 4, kp & 15, h)];
             else v = h == 0 ? b3[o] : 0.f;
+        } else if (i == hgp::kValueRowLo || i == hgp::kValueRowHi) {
+            return;
         }
     }
     pk[idx] = v;
+}
+
+// hg_set_value_head: w_v [64], b_v [1] into layer 3's A operand at tile rows 8 and 12 of each of its 33
+// k pairs (the bias in the last, k0 only) -- the elements policy_pack_kernel leaves alone.  One thread
+// per element: 33 k pairs x 2 half-waves x 2 rows.
+__global__ __launch_bounds__(kBlock) void value_pack_kernel(const float* wv, const float* bv, float* pk) {
+    const int t = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (t >= 4 * hgp::kL3Slots) return;
+    const int kp = t >> 2, h = (t >> 1) & 1, i = (t & 1) ? hgp::kValueRowHi : hgp::kValueRowLo;
+    float v;
+    if (kp < 32) v = wv[hgp::acc_row(kp >> 4, kp & 15, h)];
+    else v = h == 0 ? bv[0] : 0.f;
+    pk[hgp::kHeadFloats + 64 * (hgp::kL1Slots + hgp::kL2Slots + kp) + 32 * h + i] = v;
 }
 
 // hg_policy_act: one wave per state tile computes its envs' actions from the given observation rows
@@ -1270,6 +1350,76 @@ __global__ __launch_bounds__(64, 1) void policy_act_kernel(const float* __restri
     for (int c = 0; c < 17; ++c) o[c] = obs[i * 17 + c];
     const float4 a = hgp::policy_action(pw, pk, o, lane, seed, (uint64_t)(env_offset + i), step, epi);
     if (active) reinterpret_cast<float4*>(actions)[i] = a;
+}
+
+// hg_policy_eval: policy_act_kernel with hgp::policy_eval, the function hg_rollout_ac's kernels call: the
+// action, its log-probability and the value head's output, each stored where its pointer is not null.
+__global__ __launch_bounds__(64, 1) void policy_eval_kernel(const float* __restrict__ state, int64_t n, uint64_t seed,
+                                                            int64_t env_offset, const float* __restrict__ pk,
+                                                            const float* __restrict__ obs, float* actions, float* logp,
+                                                            float* value) {
+    const int lane = threadIdx.x;
+    const int64_t blk0 = (int64_t)blockIdx.x * 64;
+    const bool active = blk0 + lane < n;
+    const uint32_t lo = (uint32_t)(active ? lane : 0);
+    const int64_t i = blk0 + lo;
+    hgp::Weights pw;
+    hgp::load_weights(pk, lane, pw);
+    const int32_t* ctr = reinterpret_cast<const int32_t*>(state);
+    const int32_t step = ctr[tix(i, kCtrCol0 + 0)], epi = ctr[tix(i, kCtrCol0 + 2)];
+    float o[17];
+#pragma unroll
+    for (int c = 0; c < 17; ++c) o[c] = obs[i * 17 + c];
+    const hgp::Eval ev = hgp::policy_eval(pw, pk, o, lane, seed, (uint64_t)(env_offset + i), step, epi, true);
+    if (!active) return;
+    if (actions) reinterpret_cast<float4*>(actions)[i] = ev.a;
+    if (logp) logp[i] = ev.logp;
+    if (value) value[i] = ev.v;
+}
+
+// hg_gae: generalised advantage estimation over a rollout's [K,N] rows, one lane per env (each row a
+// coalesced access), from the last step back:
+//   delta_k = r_k + gamma next_value[k] - value[k]
+//   A_k = delta_k + gamma lam (terminated[k] | truncated[k] ? 0 : A_{k+1}),  A_K = 0;   ret_k = A_k + value[k]
+// The flag selects (a NaN behind an episode's end does not pass it).  Only A is carried: four steps'
+// loads and deltas are formed ahead of the four dependent multiply-adds that use them.
+__global__ __launch_bounds__(kBlock) void gae_kernel(const float* __restrict__ reward, const float* __restrict__ value,
+                                                     const float* __restrict__ next_value,
+                                                     const uint8_t* __restrict__ terminated,
+                                                     const uint8_t* __restrict__ truncated, int64_t n, int32_t nsteps,
+                                                     float gamma, float lam, float* __restrict__ adv,
+                                                     float* __restrict__ ret) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float gl = gamma * lam;
+    float A = 0.f;
+    int k = nsteps - 1;
+    for (; k >= 3; k -= 4) {
+        float d[4], v[4];
+        bool cut[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t r = (int64_t)(k - j) * n + i;
+            v[j] = value[r];
+            d[j] = fmaf(gamma, next_value[r], reward[r]) - v[j];
+            cut[j] = (terminated[r] | truncated[r]) != 0;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t r = (int64_t)(k - j) * n + i;
+            A = fmaf(gl, cut[j] ? 0.f : A, d[j]);
+            adv[r] = A;
+            if (ret) ret[r] = A + v[j];
+        }
+    }
+    for (; k >= 0; --k) {
+        const int64_t r = (int64_t)k * n + i;
+        const float v = value[r];
+        const float d = fmaf(gamma, next_value[r], reward[r]) - v;
+        A = fmaf(gl, (terminated[r] | truncated[r]) != 0 ? 0.f : A, d);
+        adv[r] = A;
+        if (ret) ret[r] = A + v;
+    }
 }
 
 // hg_debug_philox: the device Philox4x32-10 on given counters and keys, rows {c0, c1, c2, c3, k0, k1}
@@ -1628,6 +1778,7 @@ struct hg_env {
     bool env_templates = false;
     float* policy_dev = nullptr;            // the MLP policy's packed image (hg_set_policy, policy_mlp.h)
     bool policy_set = false;
+    bool value_set = false;                 // hg_set_value_head was called
     bool baked = false;                     // step with the constant-specialised kernel (baked.h)
     bool baked_allowed = true;              // ... unless switched off (hg_set_specialized)
     // a run-time specialised code object for another airframe (step_rtc.hip, hg_load_specialized)
@@ -1841,6 +1992,29 @@ static void launch_rollout_policy(const hg_env* e, hipStream_t s, const StepArgs
     } else {
         if (feat) eta ? go(rollout_policy_kernel<T, true, true, false>) : go(rollout_policy_kernel<T, false, true, false>);
         else eta ? go(rollout_policy_kernel<T, true, false, false>) : go(rollout_policy_kernel<T, false, false, false>);
+    }
+}
+// hg_rollout_ac's launch, as hg_rollout_policy's
+template <int T>
+static void launch_rollout_ac(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol, const AcArgs& ac,
+                              bool eta, bool feat) {
+    const unsigned grid = (unsigned)((e->n + 63) / 64);
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, STEP_KARGS(e), a, pol, ac); };
+    ++e->n_launch[4];
+    if (e->baked) {
+        if (feat) eta ? go(rollout_ac_kernel<T, true, true, true>) : go(rollout_ac_kernel<T, false, true, true>);
+        else eta ? go(rollout_ac_kernel<T, true, false, true>) : go(rollout_ac_kernel<T, false, false, true>);
+    } else {
+        if (feat) eta ? go(rollout_ac_kernel<T, true, true, false>) : go(rollout_ac_kernel<T, false, true, false>);
+        else eta ? go(rollout_ac_kernel<T, true, false, false>) : go(rollout_ac_kernel<T, false, false, false>);
+    }
+}
+static void dispatch_rollout_ac(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol, const AcArgs& ac,
+                                bool eta, bool feat) {
+    switch (e->cfg.task) {
+        case HG_TASK_HOVER: launch_rollout_ac<HG_TASK_HOVER>(e, s, a, pol, ac, eta, feat); break;
+        case HG_TASK_FORWARD_FLIGHT: launch_rollout_ac<HG_TASK_FORWARD_FLIGHT>(e, s, a, pol, ac, eta, feat); break;
+        default: launch_rollout_ac<HG_TASK_HELI>(e, s, a, pol, ac, eta, feat); break;
     }
 }
 static void dispatch_rollout_policy(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol, bool eta,
@@ -2551,6 +2725,99 @@ int32_t hg_rollout_policy(hg_env* e, const float* obs0, int32_t nsteps, float* a
     const bool feat = e->Pf.autoreset_next || e->Pf.max_episode_steps != INT32_MAX || e->Pf.env_templates ||
                       e->Pf.reset_retrim;
     dispatch_rollout_policy(e, (hipStream_t)stream, a, pol, eta != nullptr, feat);
+    HIP_TRY(hipGetLastError());
+    return HG_OK;
+}
+
+int32_t hg_set_value_head(hg_env* e, const float* wv, const float* bv, void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!wv || !bv) return fail(HG_E_INVALID, "hg_set_value_head: wv/bv must be device pointers");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    hipLaunchKernelGGL(value_pack_kernel, dim3(grid_for(4 * hgp::kL3Slots)), dim3(kBlock), 0, (hipStream_t)stream, wv, bv,
+                       e->policy_dev);
+    HIP_TRY(hipGetLastError());
+    e->value_set = true;
+    return HG_OK;
+}
+
+int32_t hg_policy_eval(hg_env* e, const float* obs, float* actions, float* logp, float* value, void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!e->policy_set) return fail(HG_E_INVALID, "hg_policy_eval: no policy set (hg_set_policy)");
+    if (!obs) return fail(HG_E_INVALID, "hg_policy_eval: obs must be a device pointer");
+    if (value && !e->value_set) return fail(HG_E_INVALID, "hg_policy_eval: values need a value head (hg_set_value_head)");
+    if ((uintptr_t)actions & 15) return fail(HG_E_INVALID, "actions must be 16-byte aligned");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    hipLaunchKernelGGL(policy_eval_kernel, dim3((unsigned)((e->n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, e->state,
+                       (int64_t)e->n, (uint64_t)e->cfg.seed, (int64_t)e->cfg.env_offset, e->policy_dev, obs, actions, logp,
+                       value);
+    HIP_TRY(hipGetLastError());
+    return HG_OK;
+}
+
+int32_t hg_rollout_ac(hg_env* e, const float* obs0, int32_t nsteps, float* actions_out, float* obs, float* reward,
+                      uint8_t* terminated, uint8_t* truncated, uint8_t* info, const float* eta, float* logp, float* value,
+                      float* next_value, void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!e->policy_set) return fail(HG_E_INVALID, "hg_rollout_ac: no policy set (hg_set_policy)");
+    if (nsteps < 1) return fail(HG_E_INVALID, "nsteps must be >= 1");
+    if (!obs0 || !actions_out || !obs || !reward || !terminated || !truncated)
+        return fail(HG_E_INVALID, "obs0/actions_out/obs/reward/terminated/truncated must be device pointers");
+    if (((uintptr_t)actions_out & 15) || ((uintptr_t)obs & 15))
+        return fail(HG_E_INVALID, "actions_out and obs must be 16-byte aligned");
+    if (((uintptr_t)logp & 3) || ((uintptr_t)value & 3) || ((uintptr_t)next_value & 3))
+        return fail(HG_E_INVALID, "logp, value and next_value must be 4-byte aligned");
+    if ((value != nullptr) != (next_value != nullptr))
+        return fail(HG_E_INVALID, "hg_rollout_ac: value and next_value go together (both or neither)");
+    if (value && !e->value_set) return fail(HG_E_INVALID, "hg_rollout_ac: values need a value head (hg_set_value_head)");
+    if (e->Pf.reset_retrim && e->Pf.autoreset)
+        return fail(HG_E_INVALID, "hg_rollout_ac does not support auto-resets in reset_mode RETRIM (re-trims run between steps)");
+    if (e->Pf.autoreset_next)
+        return fail(HG_E_INVALID, "hg_rollout_ac does not support HG_AUTORESET_NEXT_STEP (its filler transitions would need a validity mask)");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    e->ov_chain = kChainBroken;   // the next step's pending resets take the serial re-trim
+    e->chain_expect = kChainBroken;
+    StepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.hmap = e->hmap;
+    a.obs = obs;
+    a.reward = reward;
+    a.terminated = terminated;
+    a.truncated = truncated;
+    a.info = info;
+    a.eta = eta;
+    a.tmpl_env = e->tmpl_env;
+    a.nsteps = nsteps;
+    a.retrim_slot = -1;
+    a.retrim_wind = e->retrim_wind;   // (reset_mode RETRIM without auto-reset: as hg_rollout)
+    PolicyArgs pol;
+    pol.pk = e->policy_dev;
+    pol.obs0 = obs0;
+    pol.actions_out = actions_out;
+    AcArgs ac;
+    ac.logp = logp;
+    ac.value = value;
+    ac.next_value = next_value;
+    const bool feat = e->Pf.autoreset_next || e->Pf.max_episode_steps != INT32_MAX || e->Pf.env_templates ||
+                      e->Pf.reset_retrim;
+    dispatch_rollout_ac(e, (hipStream_t)stream, a, pol, ac, eta != nullptr, feat);
+    HIP_TRY(hipGetLastError());
+    return HG_OK;
+}
+
+int32_t hg_gae(hg_env* e, const float* reward, const float* value, const float* next_value, const uint8_t* terminated,
+               const uint8_t* truncated, int32_t nsteps, float gamma, float lam, float* adv_out, float* ret_out,
+               void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (nsteps < 1) return fail(HG_E_INVALID, "nsteps must be >= 1");
+    if (!reward || !value || !next_value || !terminated || !truncated || !adv_out)
+        return fail(HG_E_INVALID, "hg_gae: reward/value/next_value/terminated/truncated/adv_out must be device pointers");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    hipLaunchKernelGGL(gae_kernel, dim3(grid_for(e->n)), dim3(kBlock), 0, (hipStream_t)stream, reward, value, next_value,
+                       terminated, truncated, (int64_t)e->n, nsteps, gamma, lam, adv_out, ret_out);
     HIP_TRY(hipGetLastError());
     return HG_OK;
 }

@@ -23,9 +23,18 @@
 //
 // Packed device image (floats; kPolicyFloats in all), written by policy_pack_kernel:
 //   [0..3] exp(log_std) (0 when deterministic)   [4] 1.0 when stochastic, else 0.0
+//   [5] log_std[0] + log_std[1] + log_std[2] + log_std[3], summed left to right (0 when deterministic)
 //   [8..24] obs_mean (0 when absent)   [25..41] obs_scale (1 when absent)
 //   [64 + 64 s + l]  A operand of lane l for slot s: s in [0,18) layer 1 (mt * 9 + ks),
 //                    [18,84) layer 2 (mt * 33 + kp), [84,117) layer 3 (kp)
+//
+// Value head (hg_set_value_head, policy_eval): v = w_v . tanh(h2) + b_v shares the trunk and rides in
+// layer 3's tile: w_v is one more row of the A operand, at tile rows 8 and 12, which acc_row() puts in
+// accumulator register 4 of the lower and of the upper half-wave -- no further matrix instruction.  The
+// rows of D are independent, so the actions are bitwise the same with or without it.  Its elements of
+// the image (lanes 8, 12, 40, 44 of the layer-3 slots) are value_pack_kernel's and no one else's:
+// policy_pack_kernel skips them, so hg_set_policy and hg_set_value_head commute and neither undoes the
+// other.  They are zero (hg_create) until a head is set.
 #pragma once
 
 namespace hgp {
@@ -38,6 +47,9 @@ constexpr int kL3Slots = kL2Steps;
 constexpr int kSlots = kL1Slots + kL2Slots + kL3Slots;
 constexpr int kHeadFloats = 64;
 constexpr int kStdOff = 0, kStochOff = 4, kMeanOff = 8, kScaleOff = 25;
+constexpr int kLogStdSumOff = 5;            // sum of log_std (the log-probability's constant)
+constexpr int kValueRowLo = 8, kValueRowHi = 12;   // the value head's rows of layer 3's tile
+constexpr int kValueReg = 4;                // acc_row(0, 4, 0) == 8, acc_row(0, 4, 1) == 12
 constexpr int kPolicyFloats = kHeadFloats + 64 * kSlots;
 // key words of the action noise: the turbulence key (seed lo, seed hi) with these constants XORed in
 constexpr uint32_t kNoiseKey0 = 0x706F6C69u, kNoiseKey1 = 0x63795F7Au;
@@ -146,6 +158,89 @@ __device__ __forceinline__ float4 policy_action(const Weights& w, const float* _
         a.w = a.w + pk[kStdOff + 3] * z3;
     }
     return a;
+}
+
+// What policy_eval returns beside the action.
+struct Eval {
+    float4 a;     // the sampled action (the mean when nothing is drawn)
+    float logp;   // log pi(a | obs) from the z drawn; 0 when nothing is drawn
+    float v;      // w_v . tanh(h2) + b_v (0 while no value head is set)
+};
+
+// policy_action with the log-probability of the action and the value head's output.  The action is
+// bitwise policy_action's (the same instructions on the same operands; the value row is another row of
+// layer 3's D).  sample (wave-uniform): false computes the mean action and the value only and draws
+// nothing -- the rollout's value of a terminal observation.  logp = -1/2 sum z_i^2 - sum log_std_i -
+// 2 ln 2 pi with the z the noise was built from, not (a - mean) / std.
+__device__ __forceinline__ Eval policy_eval(const Weights& w, const float* __restrict__ pk, const float obs[17], int lane,
+                                            uint64_t seed, uint64_t gid, int32_t step, int32_t epi, bool sample) {
+    const bool upper = lane >= 32;
+    float x[18];
+#pragma unroll
+    for (int c = 0; c < 17; ++c) {
+        const float d = obs[c] - pk[kMeanOff + c];
+        x[c] = d * pk[kScaleOff + c];
+    }
+    x[17] = 1.0f;
+    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    f32x16 h1[2][2] = {{zero, zero}, {zero, zero}};
+#pragma unroll
+    for (int ks = 0; ks < kL1Steps; ++ks) {
+        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(x[2 * ks]), __float_as_uint(x[2 * ks + 1]),
+                                                         false, false);
+        const float b0 = __uint_as_float(sw[0]), b1 = __uint_as_float(sw[1]);
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            h1[mt][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.l1[mt * kL1Steps + ks], b0, h1[mt][0], 0, 0, 0);
+            h1[mt][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.l1[mt * kL1Steps + ks], b1, h1[mt][1], 0, 0, 0);
+        }
+    }
+    const float one_lo = upper ? 0.0f : 1.0f;
+    f32x16 h2[2][2] = {{zero, zero}, {zero, zero}};
+#pragma unroll
+    for (int kp = 0; kp < kL2Steps; ++kp) {
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+            const float b = kp < 32 ? tanh_exp(h1[kp >> 4][nt][kp & 15]) : one_lo;
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+                h2[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.l2[mt * kL2Steps + kp], b, h2[mt][nt], 0, 0, 0);
+        }
+    }
+    f32x16 o[2] = {zero, zero};
+#pragma unroll
+    for (int kp = 0; kp < kL2Steps; ++kp) {
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+            const float b = kp < 32 ? tanh_exp(h2[kp >> 4][nt][kp & 15]) : one_lo;
+            o[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.l3[kp], b, o[nt], 0, 0, 0);
+        }
+    }
+    Eval e;
+    e.a.x = upper ? o[1][0] : o[0][0];
+    e.a.y = upper ? o[1][1] : o[0][1];
+    e.a.z = upper ? o[1][2] : o[0][2];
+    e.a.w = upper ? o[1][3] : o[0][3];
+    e.v = upper ? o[1][kValueReg] : o[0][kValueReg];
+    e.logp = 0.0f;
+    if (sample && pk[kStochOff] != 0.0f) {   // (uniform) the noise exactly as policy_action draws and adds it
+        const U4 r = philox(U4{(uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)step, (uint32_t)epi},
+                            (uint32_t)seed ^ kNoiseKey0, (uint32_t)(seed >> 32) ^ kNoiseKey1);
+        const float r0 = sqrtf(__log2f(u01(r.x)) * -1.38629436111989061f);   // sqrt(-2 ln u)
+        const float r1 = sqrtf(__log2f(u01(r.z)) * -1.38629436111989061f);
+        const float a1 = __uint_as_float((r.y >> 9) | 0x3f800000u), a3 = __uint_as_float((r.w >> 9) | 0x3f800000u);
+        const float z0 = r0 * __builtin_amdgcn_cosf(a1);
+        const float z1 = r0 * __builtin_amdgcn_sinf(a1);
+        const float z2 = r1 * __builtin_amdgcn_cosf(a3);
+        const float z3 = r1 * __builtin_amdgcn_sinf(a3);
+        e.a.x = e.a.x + pk[kStdOff + 0] * z0;
+        e.a.y = e.a.y + pk[kStdOff + 1] * z1;
+        e.a.z = e.a.z + pk[kStdOff + 2] * z2;
+        e.a.w = e.a.w + pk[kStdOff + 3] * z3;
+        const float q = fmaf(z3, z3, fmaf(z2, z2, fmaf(z1, z1, z0 * z0)));
+        e.logp = fmaf(-0.5f, q, -pk[kLogStdSumOff]) - 3.67575413281869070f;   // 2 ln 2 pi
+    }
+    return e;
 }
 
 }  // namespace hgp

@@ -106,6 +106,10 @@ _SIGS = {
     "hg_set_policy": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hg_policy_act": (ctypes.c_int32, [_P, _P, _P, _P]),
     "hg_rollout_policy": (ctypes.c_int32, [_P, _P, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "hg_set_value_head": (ctypes.c_int32, [_P, _P, _P, _P]),
+    "hg_policy_eval": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P]),
+    "hg_rollout_ac": (ctypes.c_int32, [_P, _P, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "hg_gae": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_float, ctypes.c_float, _P, _P, _P]),
     "hg_trim_batch": (ctypes.c_int32, [_P, _P, ctypes.c_int64, _P, _P, _P, _P, _P]),
     "hg_retrim_failures": (ctypes.c_int32, [_P, ctypes.POINTER(ctypes.c_int64)]),
     "hg_set_retrim_overlap": (ctypes.c_int32, [_P, ctypes.c_int32]),

@@ -6,7 +6,8 @@ with W1 [64,17], W2 [64,64], W3 [4,64] row-major [out,in] as torch.nn.Linear sto
 
 `pack_policy` is a pure function that runs on the CPU: it takes the weights either as three (W, b)
 pairs or as an nn.Sequential of Linear / Tanh / Linear / Tanh / Linear, checks shapes and dtypes and
-returns contiguous fp32 tensors in the order hg_set_policy takes them.
+returns contiguous fp32 tensors in the order hg_set_policy takes them.  `pack_value_head` does the same
+for the value head v = w_v . tanh(h2) + b_v on the policy's second hidden layer (hg_set_value_head).
 """
 N_OBS, N_HIDDEN, N_ACT = 17, 64, 4
 LAYER_SHAPES = ((N_HIDDEN, N_OBS), (N_HIDDEN, N_HIDDEN), (N_ACT, N_HIDDEN))
@@ -62,3 +63,30 @@ def pack_policy(model_or_pairs, log_std=None, obs_mean=None, obs_scale=None):
         out += [w.detach().contiguous(), b.detach().contiguous()]
     return (*out, _vector(log_std, N_ACT, "log_std"), _vector(obs_mean, N_OBS, "obs_mean"),
             _vector(obs_scale, N_OBS, "obs_scale"))
+
+
+def pack_value_head(head):
+    """Validate a value head v = w_v . tanh(h2) + b_v on the policy's trunk (hg_set_value_head) and return
+    (w_v [64], b_v [1]): contiguous float32 tensors.  `head` is an nn.Linear(64, 1) or a (w, b) pair with w
+    of shape [1, 64] or [64] and b of shape [1].  Raises ValueError naming the offending shape (or dtype)."""
+    import torch
+    nn = torch.nn
+    if isinstance(head, nn.Module):
+        if not isinstance(head, nn.Linear):
+            raise ValueError(f"value head must be nn.Linear({N_HIDDEN}, 1) or a (w, b) pair, got {type(head).__name__}")
+        if head.bias is None:
+            raise ValueError(f"value head Linear with weight shape {tuple(head.weight.shape)} has no bias")
+        w, b = head.weight.detach(), head.bias.detach()
+    else:
+        pair = list(head)
+        if len(pair) != 2:
+            raise ValueError(f"value head must be nn.Linear({N_HIDDEN}, 1) or a (w, b) pair, got {len(pair)} items")
+        if pair[1] is None:
+            raise ValueError("value head has no bias: b must be float32 of shape (1,)")
+        w, b = torch.as_tensor(pair[0]), torch.as_tensor(pair[1])
+    if tuple(w.shape) not in ((1, N_HIDDEN), (N_HIDDEN,)) or tuple(b.shape) != (1,):
+        raise ValueError(f"value head: w must be (1, {N_HIDDEN}) or ({N_HIDDEN},) and b (1,), "
+                         f"got {tuple(w.shape)} and {tuple(b.shape)}")
+    if w.dtype != torch.float32 or b.dtype != torch.float32:
+        raise ValueError(f"value head: w {tuple(w.shape)} / b {tuple(b.shape)} must be float32, got {w.dtype} / {b.dtype}")
+    return w.detach().reshape(N_HIDDEN).contiguous(), b.detach().contiguous()

@@ -306,7 +306,58 @@ int32_t hg_rollout_policy(hg_env* env, const float* obs0_dev, int32_t nsteps, fl
                           float* obs_dev, float* reward_dev, uint8_t* terminated_dev, uint8_t* truncated_dev,
                           uint8_t* info_dev, const float* eta_dev, void* stream);
 
-/* Batched device trim: HelicopterDynamics.trim (helicopter_dynamics.py:491-576) of the env's trim
+/* ---- Actor-critic rollouts: what a PPO / A2C learner needs beside the actions, from the same launch.
+ *
+ * Value head (fixed):   v = w_v . tanh(h2) + b_v,   h2 = W2 tanh(W1 x + b1) + b2 the policy's second
+ * hidden layer: w_v [64], b_v [1], fp32, sharing the policy's trunk.  It is one more row of the last
+ * matrix product, so it adds no matrix instruction, and the actions are bitwise the same with or
+ * without it.  (A separate critic network is not offered: it would double the matrix work and does not
+ * fit the register file beside the actor.)
+ * Log-probability:   logp = -1/2 (z0^2 + z1^2 + z2^2 + z3^2) - (log_std0 + .. + log_std3) - 2 ln(2 pi),
+ * from the z the action was built from (not from (a - mean) / std), fp32, the squares as one fma chain;
+ * the sum of log_std is formed left to right by hg_set_policy.  0 for a deterministic policy.
+ *
+ * hg_set_value_head: copy w_v, b_v (device pointers) into the handle's policy buffer.  It and
+ * hg_set_policy write disjoint parts of that buffer: either order gives the same result and a later
+ * hg_set_policy keeps the head.  Asynchronous on `stream`, allocates nothing, capturable. */
+int32_t hg_set_value_head(hg_env* env, const float* wv_dev, const float* bv_dev, void* stream);
+
+/* hg_policy_act with two more outputs, each [N] fp32 or NULL (actions_dev may be NULL too): the
+ * log-probability of each action and the value head's V(obs).  HG_E_INVALID for value_dev while no
+ * value head is set.  The env is not modified.  The device function is hg_rollout_ac's: evaluating
+ * and stepping (hg_step) in turn is bitwise that rollout. */
+int32_t hg_policy_eval(hg_env* env, const float* obs_dev, float* actions_dev, float* logp_dev, float* value_dev,
+                       void* stream);
+
+/* hg_rollout_policy with three more [nsteps,N] fp32 outputs, each of them or NULL (value_dev and
+ * next_value_dev together or not at all; they need a value head).  The first six outputs, the env's
+ * state and its counters are bitwise hg_rollout_policy's.  With o_0 = obs0 and o_k = obs[k-1], the
+ * observation action k was computed from:
+ *   logp[k]       = log pi(a_k | o_k)
+ *   value[k]      = V(o_k)
+ *   next_value[k] = terminated[k] ? 0 : V(o'_k), where o'_k is the observation step k produced BEFORE
+ *                   any auto-reset: obs[k], unless info[k] has HG_INFO_RESET -- then the terminal
+ *                   observation hg_step_rows would put in final_obs_rows, which no other output of a
+ *                   rollout carries.  So a TimeLimit truncation bootstraps from the value of the state
+ *                   the episode was cut at, and a termination from 0.
+ * Modes: hg_rollout_policy's without HG_AUTORESET_NEXT_STEP (the filler transition of a next-step
+ * reset would need a validity mask the advantage recursion does not have): HG_E_INVALID. */
+int32_t hg_rollout_ac(hg_env* env, const float* obs0_dev, int32_t nsteps, float* actions_out_dev, float* obs_dev,
+                      float* reward_dev, uint8_t* terminated_dev, uint8_t* truncated_dev, uint8_t* info_dev,
+                      const float* eta_dev, float* logp_dev, float* value_dev, float* next_value_dev, void* stream);
+
+/* Generalised advantage estimation over [nsteps,N] rows (N the env's), from the last step back:
+ *   delta_k = reward[k] + gamma next_value[k] - value[k]
+ *   A_k     = delta_k + gamma lam ((terminated[k] | truncated[k]) ? 0 : A_{k+1}),   A_nsteps = 0
+ *   ret_k   = A_k + value[k]
+ * adv_out_dev [nsteps,N]; ret_out_dev [nsteps,N] or NULL.  The flags cut the chain by selection, so
+ * nothing (not a NaN either) crosses an episode's end.  fp32, each line one fused multiply-add.  Takes
+ * hg_rollout_ac's outputs as they are, or a caller's own critic's values.  The env is not modified. */
+int32_t hg_gae(hg_env* env, const float* reward_dev, const float* value_dev, const float* next_value_dev,
+               const uint8_t* terminated_dev, const uint8_t* truncated_dev, int32_t nsteps, float gamma, float lam,
+               float* adv_out_dev, float* ret_out_dev, void* stream);
+
+/* Batched device trim:HelicopterDynamics.trim (helicopter_dynamics.py:491-576) of the env's trim
  * condition against `count` winds at once — the reset path of reset_mode HG_RESET_RETRIM, exposed
  * for direct use.  Same Newton iteration as hg_trim (fp64, trial point rounded to fp32), with the
  * 32 Jacobian evaluations and the 10 line-search trials of each step evaluated in parallel lanes.

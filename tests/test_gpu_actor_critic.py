@@ -1,0 +1,447 @@
+"""GPU: actor-critic rollouts (hg_set_value_head, hg_policy_eval, hg_rollout_ac, hg_gae).
+
+  1. hg_rollout_ac's first six outputs, state and counters are bitwise hg_rollout_policy's, with and
+     without a value head;
+  2. its logp / value / next_value are bitwise the stepwise loop policy_evaluate -> step, next_value
+     being policy_evaluate's value of the loop's true next observation (terminal observations at their
+     reset rows), 0 where terminated; runs with TimeLimit truncations and terminations;
+  3. the value head against a float64 forward pass, measured against a float32 NumPy one;
+  4. the log-probabilities: against the host restatement of the noise, and as a learner recomputes them
+     from the stored observations and actions;
+  5. hg_gae against a float64 reverse loop, measured against the float32 loop;
+  6. set_policy / set_value_head commute, and the whole collection step in one graph;
+  7. argument errors leave the env untouched.
+Run with -m gpu."""
+import numpy as np
+import pytest
+
+from test_gpu_noise import ETA_ABS, ETA_REL
+from test_gpu_policy_rollout import (NAMES, RESET_BIT, SEED, _assert_same, _env, _golden_obs, _on_device, _set,   # noqa: F401
+                                     _z_ref, policy, torch)
+
+pytestmark = pytest.mark.gpu
+
+K = 12
+AC_NAMES = ("logp", "value", "next_value")
+LN_2PI_X2 = 2.0 * np.log(2.0 * np.pi)
+NORTH_OUT = 3300.0   # ft: past the map's half-extent (6561.68 / 2), so is_failed's bounds clause fires
+
+
+@pytest.fixture(scope="module")
+def head(torch):
+    torch.manual_seed(21)
+    return torch.nn.Linear(64, 1)
+
+
+def _endings(torch, env, n):
+    """Envs 0, 3, 6, .. start north of the map (terminated on their first step); envs 1, 4, 7, .. start at
+    episode step 4 (truncated by the TimeLimit of 5 on their first step)."""
+    s, c = env.get_state()
+    s, c = s.clone(), c.clone()
+    s[0::3, 15] = NORTH_OUT
+    c[1::3, 0] = 4
+    env.set_state(s, c)
+
+
+def _raw_rollout_ac(torch, env, k, eta=None, values=False, obs_out=None):
+    """hg_rollout_ac through the C ABI with NULL value / next_value (rollout_actor_critic always asks for
+    them).  Returns rollout_policy's six outputs and (logp, value, next_value)."""
+    from heligym_amd.vector import _ptr
+    n, f32, u8 = env.num_envs, torch.float32, torch.uint8
+    mk = lambda *s, dt=f32: torch.empty(s, dtype=dt, device="cuda:0")   # noqa: E731
+    six = [mk(k, n, 4), mk(k, n, 17) if obs_out is None else obs_out, mk(k, n), mk(k, n, dt=u8), mk(k, n, dt=u8),
+           mk(k, n, dt=u8)]
+    ac = [mk(k, n), mk(k, n) if values else None, mk(k, n) if values else None]
+    rc = env.lib.hg_rollout_ac(env._h, _ptr(env.obs), k, *(_ptr(x) for x in six), _ptr(eta), *(_ptr(x) for x in ac),
+                               env._stream())
+    env._check(rc)
+    return tuple(six), tuple(ac)
+
+
+@pytest.mark.parametrize("case,n,k,with_head", [("hover_stochastic", 200, K, True), ("hover_stochastic", 1, K, True),
+                                                ("hover_stochastic", 64, K, False), ("hover_stochastic", 200, 1, True),
+                                                ("forward_deterministic", 200, K, True),
+                                                ("forward_deterministic", 200, K, False),
+                                                ("hover_noreset_eta", 200, K, True), ("hover_noreset_eta", 64, 1, False)])
+def test_rollout_ac_leaves_the_policy_rollout_bitwise(torch, policy, head, case, n, k, with_head):
+    kw, task, stochastic, eta = {}, "hover", True, None
+    if case == "forward_deterministic":
+        task, stochastic = "forward_flight", False
+    elif case == "hover_noreset_eta":
+        kw = dict(autoreset=False)
+        g = torch.Generator().manual_seed(5)
+        eta = (10.0 * torch.randn((k, n, 3), generator=g)).to("cuda:0")
+    a, b = _env(torch, n, task, **kw), _env(torch, n, task, **kw)
+    for e in (a, b):
+        _set(e, policy, stochastic)
+        e.reset()
+        _endings(torch, e, n)
+    if with_head:
+        a.set_value_head(head)
+        out = a.rollout_actor_critic(k, eta=eta)
+        six = tuple(out[name] for name in NAMES)
+        assert torch.isfinite(out["value"]).all() and torch.isfinite(out["next_value"]).all()
+        assert torch.isfinite(out["advantages"]).all() and torch.isfinite(out["returns"]).all()
+        logp = out["logp"]
+    else:
+        six, (logp, _, _) = _raw_rollout_ac(torch, a, k, eta=eta)
+    ref = b.rollout_policy(k, eta=eta)
+    torch.cuda.synchronize()
+    for name, x, y in zip(NAMES, six, ref):
+        _assert_same(torch, x, y, (case, n, k, name))
+    (sa, ca), (sb, cb) = a.get_state(), b.get_state()
+    _assert_same(torch, sa, sb, "state")
+    _assert_same(torch, ca, cb, "counters")
+    assert torch.isfinite(logp).all()
+    assert bool((logp != 0).all()) == stochastic and bool((logp == 0).all()) == (not stochastic)
+    nterm, ntrunc = int(six[3].sum()), int(six[4].sum())
+    print(f"\n[{case} N={n} K={k} head={with_head}] bitwise rollout_policy; {nterm} terminations, {ntrunc} truncations")
+    assert nterm > 0 and (ntrunc > 0 or n == 1 and k == 1)
+    a.close()
+    b.close()
+
+
+def _stepwise_ac(torch, env, k):
+    """k times policy_evaluate(obs) then step(actions), and the value of each step's true next
+    observation: the terminal observations (info["final_obs"]) at their reset rows, obs elsewhere."""
+    obs = env.obs
+    rows = []
+    for _ in range(k):
+        act, logp, val = env.policy_evaluate(obs)
+        obs, rew, term, trunc, info = env.step(act)
+        nxt = obs.clone()
+        if env.autoreset:
+            nxt[info["reset_index"]] = info["final_obs"]
+        nv = env.policy_evaluate(nxt)[2]
+        nv = torch.where(term.view(torch.uint8) != 0, torch.zeros_like(nv), nv)
+        rows.append((act.clone(), obs.clone(), rew.clone(), term.view(torch.uint8).clone(),
+                     trunc.view(torch.uint8).clone(), env.info_u8.clone(), logp, val, nv))
+    return tuple(torch.stack(c) for c in zip(*rows))
+
+
+@pytest.mark.parametrize("n,k,autoreset", [(200, K, True), (1, K, True), (64, K, True), (200, 1, True),
+                                           (200, K, False), (64, 1, False)])
+def test_fused_actor_critic_bitwise_equals_stepwise(torch, policy, head, n, k, autoreset):
+    a, b = _env(torch, n, autoreset=autoreset), _env(torch, n, autoreset=autoreset)
+    for e in (a, b):
+        _set(e, policy)
+        e.set_value_head(head)
+        e.reset()
+        _endings(torch, e, n)
+    fused = a.rollout_actor_critic(k)
+    step = _stepwise_ac(torch, b, k)
+    torch.cuda.synchronize()
+    for name, y in zip(NAMES + AC_NAMES, step):
+        _assert_same(torch, fused[name], y, (n, k, autoreset, name))
+    (sa, ca), (sb, cb) = a.get_state(), b.get_state()
+    _assert_same(torch, sa, sb, "state")
+    _assert_same(torch, ca, cb, "counters")
+    term, trunc = fused["terminated"] != 0, fused["truncated"] != 0
+    reset = (fused["info"] & RESET_BIT) != 0
+    nterm, ntrunc, nboot = int(term.sum()), int((trunc & ~term).sum()), int((reset & ~term).sum())
+    print(f"\n[N={n} K={k} autoreset={autoreset}] bitwise; {nterm} terminations, {ntrunc} truncations, "
+          f"{nboot} terminal observations valued, {int(reset.sum())} resets")
+    assert nterm > 0 and bool((fused["next_value"][term] == 0).all())
+    if n > 1 or k > 1:
+        assert ntrunc > 0 and bool((fused["next_value"][trunc & ~term] != 0).all())
+    if autoreset:
+        assert nboot == ntrunc and int(reset.sum()) == int((term | trunc).sum())
+        if k == K:   # TimeLimit 5: every env truncated twice in 12 steps
+            assert int((trunc & ~term).sum(0).min()) >= 2
+    else:
+        assert int(reset.sum()) == 0
+    a.close()
+    b.close()
+
+
+def _forward_ac(obs, p, head, dtype):
+    """NumPy forward pass of the policy's mean action and the value head in `dtype` (weights,
+    normalisation and inputs are the float32 values, converted)."""
+    m = p["model"]
+    c = lambda t: t.detach().numpy().astype(dtype)   # noqa: E731
+    x = (obs.astype(dtype) - c(p["obs_mean"])) * c(p["obs_scale"])
+    h = np.tanh(x @ c(m[0].weight).T + c(m[0].bias))
+    h = np.tanh(h @ c(m[2].weight).T + c(m[2].bias))
+    mean = h @ c(m[4].weight).T + c(m[4].bias)
+    v = h @ c(head.weight).reshape(64) + c(head.bias)[0]
+    assert mean.dtype == dtype and v.dtype == dtype
+    return mean, v
+
+
+def _mean_bound(obs, p, head):
+    """What test_policy_values_against_float64 grants the mean action on rows `obs`: 4x the float32 NumPy
+    forward pass's max error against float64, floored at 4 ulp of the largest |mean|."""
+    ref = _forward_ac(obs, p, head, np.float64)[0]
+    err32 = np.abs(_forward_ac(obs, p, head, np.float32)[0].astype(np.float64) - ref).max()
+    return max(4 * err32, 4 * float(np.spacing(np.float32(np.abs(ref).max()))))
+
+
+def test_values_against_float64(torch, policy, head):
+    """policy_evaluate's value on the golden observation rows of test_policy_values_against_float64, same
+    yardstick: the kernel's max abs error against the float64 forward pass <= 4x the float32 NumPy forward
+    pass's, floored at 4 ulp of the largest |value|."""
+    n = 200
+    rows = _golden_obs()
+    obs = rows[np.linspace(0, len(rows) - 1, n).astype(int)]
+    env = _env(torch, n)
+    _set(env, policy, stochastic=False)
+    env.set_value_head(head)
+    env.reset()
+    act, logp, val = env.policy_evaluate(torch.as_tensor(obs, device="cuda:0"))
+    _assert_same(torch, act, env.policy_act(torch.as_tensor(obs, device="cuda:0")), "actions are policy_act's")
+    assert bool((logp == 0).all())   # a deterministic policy
+    got = val.cpu().numpy().astype(np.float64)
+    ref = _forward_ac(obs, policy, head, np.float64)[1]
+    err32 = np.abs(_forward_ac(obs, policy, head, np.float32)[1].astype(np.float64) - ref).max()
+    err = np.abs(got - ref).max()
+    floor = 4 * float(np.spacing(np.float32(np.abs(ref).max())))
+    print(f"\n[value head] kernel max|d| {err:.3e}, float32 NumPy max|d| {err32:.3e}, ratio {err / err32:.2f} "
+          f"(bound 4; floor {floor:.3e}; max|v| {np.abs(ref).max():.3f})")
+    assert np.abs(ref).max() > 0.05 and np.abs(ref).std() > 0.01   # a non-trivial function of the rows
+    assert err <= max(4 * err32, floor)
+    env.close()
+
+
+def _ulp32(x):
+    return np.spacing(np.abs(x).astype(np.float32)).astype(np.float64)
+
+
+@pytest.mark.parametrize("log_std", [(0.0, 0.0, 0.0, 0.0), (-1.0, -0.7, 0.4, -0.9)])
+def test_logp_against_the_host_noise(torch, log_std):
+    """Zero weights: logp = -1/2 sum z^2 - sum log_std - 2 ln 2 pi with z from the host Philox / Box-Muller
+    restatement in float64.  z_i is known to t_i = ETA_ABS + ETA_REL |z_i| (test_gpu_noise), so z_i^2 / 2 to
+    |z_i| t_i + t_i^2 / 2; the fp32 evaluation is allowed 8 ulp of |logp|."""
+    n, off = 200, (1 << 33) + 5
+    z = lambda *s: torch.zeros(s)   # noqa: E731
+    rng = np.random.RandomState(9)
+    ctr = np.zeros((n, 3), np.int32)
+    ctr[:, 0] = rng.randint(0, 5000, size=n)
+    ctr[:, 2] = rng.randint(0, 1 << 20, size=n)
+    ls = np.asarray(log_std, dtype=np.float32)
+    env = _env(torch, n, env_offset=off)
+    env.set_policy([(z(64, 17), z(64)), (z(64, 64), z(64)), (z(4, 64), z(4))], log_std=torch.as_tensor(ls))
+    env.set_value_head((z(64), z(1)))
+    env.set_state(counters=ctr)
+    act, logp, val = env.policy_evaluate()
+    got = logp.cpu().numpy().astype(np.float64)
+    zr = _z_ref(off + np.arange(n), ctr[:, 0], ctr[:, 2], SEED)
+    ref = -0.5 * (zr ** 2).sum(1) - ls.astype(np.float64).sum() - LN_2PI_X2
+    t = ETA_ABS + ETA_REL * np.abs(zr)
+    tol = (np.abs(zr) * t + 0.5 * t * t).sum(1) + 8 * _ulp32(ref)
+    err = np.abs(got - ref)
+    print(f"\n[logp, log_std {log_std}] max|d| {err.max():.3e}, max |d|/tol {(err / tol).max():.3f}")
+    assert np.all(err <= tol), np.argwhere(err > tol)[:10]
+    assert bool((val == 0).all())
+    np.testing.assert_allclose(act.cpu().numpy(), np.exp(ls.astype(np.float64)) * zr, rtol=1e-5, atol=2e-4)
+    env.close()
+
+
+def test_logp_as_a_learner_recomputes_it(torch, policy, head):
+    """Normal(mean64(o_k), std).log_prob(a_k).sum(-1) in float64 from the rollout's stored observations and
+    actions.  The recomputed z_i = (a_i - mean_i) / std_i differs from the kernel's by at most
+    d_i = (ulp32(a_i) / 2 + e_mean) / std_i (the action's rounding, the mean's error as
+    test_policy_values_against_float64 bounds it), so z_i^2 / 2 by (|z_i| + d_i / 2) d_i; plus 8 ulp of
+    |logp| for the fp32 evaluation.  std is the float32 exp(log_std), as a float32 learner holds it."""
+    n = 200
+    env = _env(torch, n)
+    _set(env, policy)
+    env.set_value_head(head)
+    obs0 = env.reset()[0].clone()
+    out = env.rollout_actor_critic(K, obs0=obs0)
+    obs_in = torch.cat([obs0[None], out["obs"][:-1]]).cpu().numpy().reshape(-1, 17)
+    a = out["actions"].cpu().numpy().astype(np.float64).reshape(-1, 4)
+    got = out["logp"].cpu().numpy().astype(np.float64).reshape(-1)
+    mean = _forward_ac(obs_in, policy, head, np.float64)[0]
+    e_mean = _mean_bound(obs_in, policy, head)
+    std = np.exp(policy["log_std"].numpy()).astype(np.float64)
+    zz = (a - mean) / std
+    ref = (-0.5 * zz ** 2 - np.log(std) - 0.5 * np.log(2 * np.pi)).sum(1)
+    d = (0.5 * _ulp32(a) + e_mean) / std
+    tol = ((np.abs(zz) + 0.5 * d) * d).sum(1) + 8 * _ulp32(ref)
+    err = np.abs(got - ref)
+    print(f"\n[learner's logp] max|d| {err.max():.3e}, worst |d|/bound {(err / tol).max():.3f} "
+          f"(e_mean {e_mean:.3e}, max|z| {np.abs(zz).max():.2f})")
+    assert np.abs(zz).max() > 2.5 and np.all(err <= tol), np.argwhere(err > tol)[:10]
+    env.close()
+
+
+def _gae_loop(r, v, nv, done, gamma, lam, dtype):
+    """The recursion of include/heligym_amd.h as a NumPy reverse loop in `dtype`."""
+    r, v, nv = r.astype(dtype), v.astype(dtype), nv.astype(dtype)
+    gamma, gl = dtype(gamma), dtype(gamma) * dtype(lam)
+    adv = np.empty_like(r)
+    nxt = np.zeros(r.shape[1], dtype)
+    for k in range(r.shape[0] - 1, -1, -1):
+        delta = r[k] + gamma * nv[k] - v[k]
+        nxt = delta + gl * np.where(done[k], dtype(0), nxt)
+        adv[k] = nxt
+    assert adv.dtype == dtype
+    return adv
+
+
+@pytest.fixture(scope="module")
+def gae_inputs():
+    """Random rewards, values and flags for K = 12 (K = 1: the first row), N = 200: about 10 % terminated,
+    about 10 % truncated, a few both; next_value 0 where terminated."""
+    rng = np.random.RandomState(17)
+    k, n = K, 200
+    r = rng.standard_normal((k, n)).astype(np.float32)
+    v = (3.0 * rng.standard_normal((k, n))).astype(np.float32)
+    nv = (3.0 * rng.standard_normal((k, n))).astype(np.float32)
+    term = rng.random_sample((k, n)) < 0.10
+    trunc = rng.random_sample((k, n)) < 0.10
+    both = rng.random_sample((k, n)) < 0.02
+    term, trunc = term | both, trunc | both
+    nv[term] = 0.0
+    assert (term & trunc).sum() >= 3 and (term[0] | trunc[0]).any()
+    return r, v, nv, term, trunc
+
+
+@pytest.mark.parametrize("n", [200, 1])
+@pytest.mark.parametrize("k", [K, 1])
+@pytest.mark.parametrize("gamma,lam", [(0.99, 0.95), (1.0, 1.0), (0.9, 0.0)])
+def test_gae_against_float64(torch, gae_inputs, n, k, gamma, lam):
+    """hg_gae against the float64 reverse loop.  Yardstick: the same loop in float32; the kernel's max error
+    <= 4x that, floored at 4 ulp of max |A|.  lam = 0: A = delta, three roundings at most half an ulp of
+    |r| + gamma |next_value| + |value| each: within 2 ulp of that sum.  returns = advantages + value, one
+    float32 addition."""
+    r, v, nv, term, trunc = (x[:k, :n] for x in gae_inputs)
+    env = _env(torch, n)
+    dev = lambda x: torch.as_tensor(np.ascontiguousarray(x), device="cuda:0")   # noqa: E731
+    adv, ret = env.gae(dev(r), dev(v), dev(nv), dev(term), dev(trunc.astype(np.uint8)), gamma=gamma, lam=lam)
+    adv, ret = adv.cpu().numpy(), ret.cpu().numpy()
+    done = term | trunc
+    ref = _gae_loop(r, v, nv, done, gamma, lam, np.float64)
+    err32 = np.abs(_gae_loop(r, v, nv, done, gamma, lam, np.float32).astype(np.float64) - ref).max()
+    err = np.abs(adv.astype(np.float64) - ref).max()
+    floor = 4 * float(np.spacing(np.float32(np.abs(ref).max())))
+    print(f"\n[gae N={n} K={k} gamma={gamma} lam={lam}] kernel max|d| {err:.3e}, float32 loop {err32:.3e} "
+          f"(floor {floor:.3e}, max|A| {np.abs(ref).max():.2f})")
+    assert err <= max(4 * err32, floor)
+    np.testing.assert_array_equal(ret.view(np.int32), (adv + v).view(np.int32))
+    if lam == 0.0:
+        delta = r.astype(np.float64) + np.float64(np.float32(gamma)) * nv - v
+        mag = np.abs(r).astype(np.float64) + gamma * np.abs(nv) + np.abs(v)
+        assert np.all(np.abs(adv - delta) <= 2 * _ulp32(mag))
+    env.close()
+
+
+def test_gae_flags_cut_the_chain(torch, gae_inputs):
+    """A NaN in the step after an episode's end reaches that step's advantage and no earlier one: the rows
+    before it are bitwise those of the run without the NaN (terminated and truncated each cut)."""
+    r, v, nv, term, trunc = (x.copy() for x in gae_inputs)
+    n = r.shape[1]
+    term[K - 3, 0::2], trunc[K - 3, 0::2] = True, False
+    term[K - 3, 1::2], trunc[K - 3, 1::2] = False, True
+    env = _env(torch, n)
+    dev = lambda x: torch.as_tensor(np.ascontiguousarray(x), device="cuda:0")   # noqa: E731
+    args = lambda rr: (dev(rr), dev(v), dev(nv), dev(term), dev(trunc.astype(np.uint8)))   # noqa: E731
+    clean = env.gae(*args(r), gamma=0.99, lam=0.95)[0].cpu().numpy()
+    bad = r.copy()
+    bad[K - 2] = np.nan
+    got = env.gae(*args(bad), gamma=0.99, lam=0.95)[0].cpu().numpy()
+    assert np.isnan(got[K - 2]).all() and np.isfinite(got[:K - 2]).all()
+    np.testing.assert_array_equal(got[:K - 2].view(np.int32), clean[:K - 2].view(np.int32))
+    np.testing.assert_array_equal(got[K - 1].view(np.int32), clean[K - 1].view(np.int32))   # (behind the NaN)
+    env.close()
+
+
+def test_pack_order_and_one_graph(torch, policy, head):
+    """set_policy then set_value_head evaluates bitwise as the reverse order, and a second set_policy keeps
+    the head.  set_policy + set_value_head + rollout_actor_critic(12) captured into one graph and replayed
+    twice: bitwise the eager calls on a twin env."""
+    n = 200
+    a, b, c = _env(torch, n), _env(torch, n), _env(torch, n)
+    a.set_value_head(head)
+    _set(a, policy)
+    _set(b, policy)
+    b.set_value_head(head)
+    _set(c, policy, stochastic=False)
+    c.set_value_head(head)
+    _set(c, policy)   # (another policy image before: the second set_policy must rewrite all but the head)
+    cur = [e.reset()[0].clone() for e in (a, b, c)]
+    ea, eb, ec = (e.policy_evaluate(o) for e, o in zip((a, b, c), cur))
+    for name, x, y, z in zip(("actions", "logp", "value"), ea, eb, ec):
+        _assert_same(torch, x, y, ("order", name))
+        _assert_same(torch, x, z, ("second set_policy", name))
+    assert bool((ea[2] != 0).all()) and bool((ea[1] != 0).all())
+    c.close()
+    dev = _on_device(policy)
+    hd = (head.weight.detach().to("cuda:0"), head.bias.detach().to("cuda:0"))
+    out = a.rollout_actor_critic(K, obs0=cur[0])   # (buffers to reuse; the twin takes the same steps)
+    b.rollout_actor_critic(K, obs0=cur[1])
+    cur = [e.reset()[0].clone() for e in (a, b)]
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        _set(a, dev)
+        a.set_value_head(hd)
+        assert a.rollout_actor_critic(K, obs0=cur[0], out=out) is out
+    for rep in range(2):
+        g.replay()
+        _set(b, dev)
+        b.set_value_head(hd)
+        ref = b.rollout_actor_critic(K, obs0=cur[1])
+        torch.cuda.synchronize()
+        for name in a.AC_KEYS:
+            _assert_same(torch, out[name], ref[name], (rep, name))
+        cur[0].copy_(out["obs"][-1])
+        cur[1].copy_(ref["obs"][-1])
+    (sa, ca), (sb, cb) = a.get_state(), b.get_state()
+    _assert_same(torch, sa, sb, "state")
+    _assert_same(torch, ca, cb, "counters")
+    assert int(ca[:, 2].min()) >= 2 + 4   # two reset() and two TimeLimit resets per rollout
+    a.close()
+    b.close()
+
+
+def test_errors_leave_the_env_untouched(torch, policy, head):
+    from heligym_amd._abi import HeliGymError
+    n = 200
+
+    def unchanged(env, call, match="error -1"):
+        env.reset()
+        s0, c0 = env.get_state()
+        with pytest.raises(HeliGymError, match=match):
+            call()
+        s1, c1 = env.get_state()
+        _assert_same(torch, s0, s1, "state")
+        _assert_same(torch, c0, c1, "counters")
+
+    env = _env(torch, n)
+    unchanged(env, lambda: env.rollout_actor_critic(K), "no policy set")
+    unchanged(env, lambda: env.policy_evaluate(), "no policy set")
+    _set(env, policy)
+    unchanged(env, lambda: env.rollout_actor_critic(K), "value head")   # values requested with no head set
+    unchanged(env, lambda: env.policy_evaluate(), "value head")
+    six, (logp, _, _) = _raw_rollout_ac(torch, env, K)   # (without values it runs)
+    assert torch.isfinite(logp).all()
+    env.set_value_head(head)
+    good = env.rollout_actor_critic(K)
+
+    def half(which):   # value without next_value, and the reverse
+        from heligym_amd.vector import _ptr
+        p = {name: _ptr(good[name]) for name in env.AC_KEYS}
+        p[which] = None
+        env._check(env.lib.hg_rollout_ac(env._h, _ptr(env.obs), K, p["actions"], p["obs"], p["reward"], p["terminated"],
+                                         p["truncated"], p["info"], None, p["logp"], p["value"], p["next_value"],
+                                         env._stream()))
+    unchanged(env, lambda: half("next_value"), "go together")
+    unchanged(env, lambda: half("value"), "go together")
+    big = torch.empty((K * n * 17 + 4,), dtype=torch.float32, device="cuda:0")
+    bad = dict(good, obs=big[1:1 + K * n * 17].view(K, n, 17))   # obs 4 bytes off a 16-byte boundary
+    assert bad["obs"].data_ptr() % 16 == 4
+    unchanged(env, lambda: env.rollout_actor_critic(K, out=bad), "16-byte aligned")
+    env.close()
+    env = _env(torch, n, autoreset_mode="next_step")
+    _set(env, policy)
+    env.set_value_head(head)
+    unchanged(env, lambda: env.rollout_actor_critic(K), "NEXT_STEP")
+    env.close()
+    env = _env(torch, n, reset_mode="retrim", max_episode_steps=None)
+    _set(env, policy)
+    env.set_value_head(head)
+    unchanged(env, lambda: env.rollout_actor_critic(K), "RETRIM")   # auto-resets that re-trim run between steps
+    env.close()
