@@ -397,6 +397,16 @@ struct AcArgs {
     float* next_value = nullptr;   // terminated[k] ? 0 : V(o'_k), o'_k step k's observation before any reset
 };
 
+// hg_rollout_branch's arguments beside StepArgs (of which it reads hmap, actions and nsteps); the kernel's
+// row count N * branches travels as its `n`.  A struct of its own, like the two above.
+struct BranchArgs {
+    float* ret = nullptr;              // [N*branches] discounted return of each row
+    int32_t* alive_steps = nullptr;    // [N*branches] steps up to and including the row's ending step, or NULL
+    uint8_t* end_info = nullptr;       // [N*branches] the ending step's HG_INFO_* bits (0: survived), or NULL
+    uint32_t branches = 1;             // rows per env: row r is branch r % branches of env r / branches
+    float gamma = 1.f;
+};
+
 // TASK: reward / success of the task; ETA: noise injected by the caller (else in-kernel Philox);
 // NT: streaming output stores (see st_out); FEAT: the optional features (reset-info compaction,
 // per-reset re-trim, next-step auto-reset, TimeLimit) -- without them the kernel carries none of
@@ -415,14 +425,21 @@ struct AcArgs {
 // step k did not reset, that is the next iteration's V, stored one step late (the last step's by one
 // more forward pass after the steps); where it reset, the terminal observation is about to be
 // overwritten and is evaluated at once, in a wave-uniform branch only waves with such a lane take.
+// BRANCH (with MULTI and FEAT: hg_rollout_branch): a lane is a row of the N * branches candidates
+// (n_p their number), `branches` consecutive rows start from one env's state, which each lane loads
+// from that env's tile slot and nobody writes back.  A row is stepped as above up to its first ending
+// step and never reset; nothing is stored per step, the discounted return, the step count and the
+// ending step's info bits once at the end.  ETA here means no noise (eta = 0), not injected noise.
 template <int TASK, bool ETA, bool NT, bool FEAT, bool MULTI, bool BAKED, bool NTS, int HELP = 0, bool POLICY = false,
-          bool AC = false>
+          bool AC = false, bool BRANCH = false>
 __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p,
                                           ParamArg Pa, const Template<float>* __restrict__ Tp, const StepArgs& a,
-                                          int64_t bid, const PolicyArgs& pol = PolicyArgs{}, const AcArgs& ac = AcArgs{}) {
+                                          int64_t bid, const PolicyArgs& pol = PolicyArgs{}, const AcArgs& ac = AcArgs{},
+                                          const BranchArgs& br = BranchArgs{}) {
     static_assert(HELP == 0 || (!ETA && !MULTI), "wind helper waves: in-kernel noise, one step per launch");
     static_assert(!POLICY || (MULTI && HELP == 0), "the in-kernel policy belongs to the rollout");
     static_assert(!AC || POLICY, "log-probabilities and values are the in-kernel policy's");
+    static_assert(!BRANCH || (MULTI && FEAT && HELP == 0 && !POLICY), "branched rollouts: the open-loop rollout's steps");
     // the policy's matrix products take the wave's 64 envs as their columns: a block is one wave
     static_assert(!POLICY || kStepBlock == 64, "hg_rollout_policy needs one-wave step blocks (HG_STEP_BLOCK 64)");
     __shared__ float s_obs[(HELP ? HELP * 64 : kStepBlock) * HG_N_OBS];   // one 64-row slice per wave
@@ -496,7 +513,17 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
     // ends: a load issued near the stage-4 code makes the compiler wait for it there)
     // the helper kernel: every lane loads (the device copy is padded to one float per lane, kTplAlloc),
     // no divergent load (4 096 envs 5.20 -> 5.15 us; the other kernels measured slower so)
-    const float tpl = (HELP > 0 && HG_TPL_FULL_HELP) || lane < kTplFloats ? reinterpret_cast<const float*>(Tp)[lane] : 0.f;
+    // (BRANCH: never a reset, no template)
+    const float tpl = BRANCH ? 0.f
+                             : ((HELP > 0 && HG_TPL_FULL_HELP) || lane < kTplFloats ? reinterpret_cast<const float*>(Tp)[lane] : 0.f);
+    // BRANCH: the env this lane's row branches from (rows past the end take row blk0's), and its state
+    // groups where its tile keeps them: per-lane 16-byte loads, up to 64 lanes of one address
+    uint32_t b_env = 0;
+    const f32x4* b_st = nullptr;
+    if constexpr (BRANCH) {
+        b_env = (uint32_t)(blk0 + lo) / br.branches;   // (rows < 2^31: checked by the host)
+        b_st = reinterpret_cast<const f32x4*>(state_p + (int64_t)(b_env / kTileEnvs) * kTileWords) + b_env % kTileEnvs;
+    }
     // The state groups in the order they are needed (retrim.h slot table): position and step
     // counter (-> terrain texel address, noise key), the rest of the key and the carry, the wind
     // state (-> wind step), then the heli state.  hs[2], hs[3] (the rotor azimuths) are not stepped.
@@ -505,10 +532,16 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
     {
         // (HELP: group 2 -- carry[1..2], wind state -- is the helper wave's; the carry is rewritten
         // at the end of every step and the wind state comes back from the helper)
-        const f32x4 g0 = ld_lane(GRP(st_b, 0), lt), g1 = ld_lane(GRP(st_b, 1), lt),
-                    g2 = HELP ? f32x4{0.f, 0.f, 0.f, 0.f} : ld_lane(GRP(st_b, 2), lt),
-                    g3 = ld_lane(GRP(st_b, 3), lt), g4 = ld_lane(GRP(st_b, 4), lt), g5 = ld_lane(GRP(st_b, 5), lt),
-                    g6 = ld_lane(GRP(st_b, 6), lt);
+        f32x4 g0, g1, g2, g3, g4, g5, g6;
+        if constexpr (BRANCH) {
+            g0 = b_st[0 * kTileEnvs]; g1 = b_st[1 * kTileEnvs]; g2 = b_st[2 * kTileEnvs]; g3 = b_st[3 * kTileEnvs];
+            g4 = b_st[4 * kTileEnvs]; g5 = b_st[5 * kTileEnvs]; g6 = b_st[6 * kTileEnvs];
+        } else {
+            g0 = ld_lane(GRP(st_b, 0), lt); g1 = ld_lane(GRP(st_b, 1), lt);
+            g2 = HELP ? f32x4{0.f, 0.f, 0.f, 0.f} : ld_lane(GRP(st_b, 2), lt);
+            g3 = ld_lane(GRP(st_b, 3), lt); g4 = ld_lane(GRP(st_b, 4), lt); g5 = ld_lane(GRP(st_b, 5), lt);
+            g6 = ld_lane(GRP(st_b, 6), lt);
+        }
         hs[15] = g0.x; hs[16] = g0.y; hs[17] = g0.z; step = __float_as_int(g0.w);
         epi = __float_as_int(g1.x); succ = __float_as_int(g1.y); carry[3] = g1.z; carry[0] = g1.w;
         carry[1] = g2.x; carry[2] = g2.y; ws[0] = g2.z; ws[1] = g2.w;
@@ -525,14 +558,21 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
     // (data-independent: issued ahead of the first wait for the state, off the step's critical path)
     const hg::StepK Kpairs = hg::step_k<NT && HG_PIN_CONSTANTS>(BAKED ? PB : P0);
 #endif
-    if (FEAT && bid == 0 && tid == 0) {   // counters of a later step (rings of three)
+    if (FEAT && !BRANCH && bid == 0 && tid == 0) {   // counters of a later step (rings of three)
         if (a.reset_count_next) *a.reset_count_next = 0;
         if (a.retrim_slot >= 0 && a.retrim_count) a.retrim_count[a.retrim_slot == 2 ? 0 : a.retrim_slot + 1] = 0;
         if (a.ov_count_next) *a.ov_count_next = 0;
     }
-    if (FEAT && bid == 0 && a.fused_next && tid < kFusedWaveCtrs + 1) a.fused_next[kFusedLine * tid] = 0;
-    if (FEAT && bid == 0 && a.fused_next && tid < 2) a.fused_next[1 + tid] = 0;
+    if (FEAT && !BRANCH && bid == 0 && a.fused_next && tid < kFusedWaveCtrs + 1) a.fused_next[kFusedLine * tid] = 0;
+    if (FEAT && !BRANCH && bid == 0 && a.fused_next && tid < 2) a.fused_next[1 + tid] = 0;
     const int nsteps = MULTI ? a.nsteps : 1;
+    // BRANCH: the row's return and discount, its steps so far, its ending step's info bits; a row is
+    // alive until its first ending step.  The rows of an env waiting for its next-step reset (whose next
+    // step ignores the action) are over before they start.
+    float br_G = 0.f, br_disc = 1.f;
+    int32_t br_T = 0;
+    uint32_t br_end = 0;
+    bool br_alive = BRANCH && active && !(P0.autoreset_next && step < 0);
     bool defer_st = false;   // (one step per launch) a deferred reset: the step counter alone is stored
     // the re-trim queue (below): the wave's job mask, the slot counter's old value (leader lane), this
     // lane's job and its trim wind
@@ -646,7 +686,14 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
     } else {
     // turbulence noise (wind_dynamics.py:49-52): injected, or Philox normals
     float eta[3];
-    draw_eta<ETA>(a, seed_p, envoff_p, P, so, blk0, lo, step, epi, eta);
+    if constexpr (BRANCH) {
+        // the env's own noise, whichever row this is (keyed by its global id and the row's counters, which
+        // advance as the env's will), or none
+        if constexpr (ETA) eta[0] = eta[1] = eta[2] = 0.f;
+        else draw_eta<false>(a, seed_p, envoff_p, P, 0, (int64_t)b_env, 0u, step, epi, eta);
+    } else {
+        draw_eta<ETA>(a, seed_p, envoff_p, P, so, blk0, lo, step, epi, eta);
+    }
 
     // ground height under the committed position (F6), wind step (Heli.step :195-199)
     TSTAMP(2, "v"(eta[2]), "v"(eta[0]));
@@ -672,7 +719,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
     const hg::GroundTexels tex_p = hg::ground_fetch(a.hmap, cell_p);
 #endif
     TSTAMP(8, "v"(hs[8]), "v"(hs[11]), "v"(obs[16]));
-    if (FEAT && P.reset_retrim && active && !(P.autoreset_next && step < 0)) {   // F8: a reset trims against this wind
+    if (FEAT && !BRANCH && P.reset_retrim && active && !(P.autoreset_next && step < 0)) {   // F8: a reset trims against this wind
         float* wb = a.retrim_wind + blk0;   // [3][N]: three coalesced rows
         st_lane<false>(wb, (uint32_t)tid, W[0]);
         st_lane<false>(wb + n, (uint32_t)tid, W[1]);
@@ -719,11 +766,29 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
     const bool successed = succ >= P.success_steps;   // successed_time before this step's add
     const bool time_up = step >= P.time_up_steps;
     // next-step auto-reset: an env that ended last step (counter -(n + 1)) only resets this step
-    const bool pending = FEAT && P.autoreset_next && waiting;
+    const bool pending = FEAT && !BRANCH && P.autoreset_next && waiting;   // (BRANCH: such a row is not alive)
     const bool term = (failed || successed) && !pending;
     const bool trunc = (time_up || (FEAT && step >= P.max_episode_steps)) && !pending;   // + TimeLimit
     const bool done = term || trunc;
     succ += success_step ? 1 : 0;
+
+    if constexpr (BRANCH) {
+        // the row's accumulation, masked by select: a row past its end keeps stepping beside its live
+        // neighbours (physics.h clamps the terrain indices of a non-finite position) and adds nothing
+        br_G = br_alive ? fmaf(br_disc, rew, br_G) : br_G;
+        br_disc = br_disc * br.gamma;
+        br_T += br_alive ? 1 : 0;
+        br_end = (br_alive && done) ? (uint32_t)((failed ? HG_INFO_FAILED : 0) | (successed ? HG_INFO_SUCCESSED : 0) |
+                                                 (time_up ? HG_INFO_TIME_UP : 0) | (success_step ? HG_INFO_SUCCESS_STEP : 0))
+                                    : br_end;
+        br_alive = br_alive && !done;
+        if (!__any(br_alive)) break;   // (wave-uniform)
+        carry[0] = obs[4];
+        carry[1] = obs[5];
+        carry[2] = obs[6];
+        carry[3] = obs[16];
+        continue;   // no outputs per step, no reset
+    }
 
     // auto-reset (same step, or the step after the end)
     const bool do_reset = P.autoreset && active && ((FEAT && P.autoreset_next) ? pending : done);
@@ -916,6 +981,14 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
         for (int c = 0; c < 17; ++c) pobs[c] = obs[c];
     }
     }   // steps
+    if constexpr (BRANCH) {   // the row's three results; the env's state stays as it was read
+        if (active) {
+            st_lane<kNTS>(br.ret + blk0, (uint32_t)tid, br_G);
+            if (br.alive_steps) st_lane<kNTS>(br.alive_steps + blk0, (uint32_t)tid, br_T);
+            if (br.end_info) st_lane<kNTS>(br.end_info + blk0, (uint32_t)tid, (uint8_t)br_end);
+        }
+        return;
+    }
     TSTAMP(13, "v"(hs[0]), "v"(carry[3]));
     st_b = reinterpret_cast<f32x4*>(state_p + tile * kTileWords) + 4 * kTileEnvs;
     asm volatile("" : "+s"(st_b));
@@ -1015,6 +1088,121 @@ __global__ __launch_bounds__(64, 1) void rollout_ac_kernel(float* __restrict__ s
                                                            const PolicyArgs pol, const AcArgs ac) {
     step_body<TASK, ETA, true, FEAT, true, BAKED, false, 0, true, true>(state_p, n_p, seed_p, envoff_p, Pa, Tp, a,
                                                                         blockIdx.x, pol, ac);
+}
+
+// hg_rollout_branch: the rollout's steps on N * branches rows that start from the N envs' states
+// (step_body's BRANCH).  A wave takes 64 consecutive rows; `rows_p` stands where the step kernels have
+// their env count.  It reads each env's state once, keeps the steps in registers and writes three words
+// per row at the end: nothing per step, so it is compute bound where the other rollouts are store
+// bound.  NOISE_OFF: eta = 0 (HG_BRANCH_NOISE_OFF), else the env's own noise.
+// WAVES: the waves per SIMD the kernel's registers must fit.  1 and 2 are the lone-wave (NT) step, for
+// rows up to one and up to two waves per SIMD: the constant-specialised step takes 258 to 266 registers
+// when unbound and 256 with 36 to 40 bytes of scratch when bound to two waves, and each is the faster
+// one at its size (64 branches x 1 024 envs x 50 steps: 166 against 175 us; x 2 048 envs, where the
+// unbound one runs its second wave after the first: 321 against 295 us).  The generic step fits two waves
+// either way, so only its WAVES 2 is built.  3 is the bulk step, past two waves per SIMD.
+template <int TASK, bool NOISE_OFF, int WAVES, bool BAKED>
+__global__ __launch_bounds__(kStepBlock, WAVES) void rollout_branch_kernel(
+    float* __restrict__ state_p, int64_t rows_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
+    const Template<float>* __restrict__ Tp, const StepArgs a, const BranchArgs br) {
+    static_assert(WAVES >= 1 && WAVES <= 3, "WAVES 1, 2: the lone-wave step; 3: the bulk step");
+    step_body<TASK, NOISE_OFF, (WAVES < 3), true, true, BAKED, false, 0, false, false, true>(
+        state_p, rows_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, PolicyArgs{}, AcArgs{}, br);
+}
+
+// hg_mppi_sample: candidate action sequences around a nominal one, element-wise over [horizon, N*branches]:
+// a[t, r] = clamp(nominal[t, e] + sigma * z, lo, hi), e = r / branches, b = r % branches; branch 0 is the
+// clamped nominal (no perturbation).  z: four normals of one Philox4x32-10 call on (gid_lo, gid_hi, t, b),
+// gid = env_offset + e, keyed by the caller's sample seed; Box-Muller as the policy noise's
+// (policy_mlp.h), unit variance.
+struct MppiBox {
+    float sigma[4], lo[4], hi[4];
+};
+__global__ __launch_bounds__(kBlock) void mppi_sample_kernel(const float4* __restrict__ nominal, int64_t n, uint32_t branches,
+                                                             int32_t horizon, int64_t env_offset, uint64_t seed,
+                                                             const MppiBox box, float4* __restrict__ out) {
+    const int64_t rows = n * branches;
+    const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (idx >= rows * horizon) return;
+    const uint32_t t = (uint32_t)(idx / rows), r = (uint32_t)(idx - (int64_t)t * rows);
+    const uint32_t e = r / branches, b = r - e * branches;
+    const float4 m = nominal[(int64_t)t * n + e];
+    float v[4] = {m.x, m.y, m.z, m.w};
+    if (b != 0) {
+        const uint64_t gid = (uint64_t)(env_offset + e);
+        const U4 q = philox(U4{(uint32_t)gid, (uint32_t)(gid >> 32), t, b}, (uint32_t)seed, (uint32_t)(seed >> 32));
+        const float r0 = sqrtf(__log2f(u01(q.x)) * -1.38629436111989061f);   // sqrt(-2 ln u)
+        const float r1 = sqrtf(__log2f(u01(q.z)) * -1.38629436111989061f);
+        const float a1 = __uint_as_float((q.y >> 9) | 0x3f800000u), a3 = __uint_as_float((q.w >> 9) | 0x3f800000u);
+        const float z[4] = {r0 * __builtin_amdgcn_cosf(a1), r0 * __builtin_amdgcn_sinf(a1), r1 * __builtin_amdgcn_cosf(a3),
+                            r1 * __builtin_amdgcn_sinf(a3)};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[c] = fmaf(box.sigma[c], z[c], v[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) v[c] = fminf(fmaxf(v[c], box.lo[c]), box.hi[c]);
+    out[idx] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// hg_mppi_update: the softmax-weighted mean of an env's candidates, one wave per env (the result does not
+// depend on N, on the env's place or on the launch shape).  The wave finds the largest finite return with
+// a wave reduction and leaves the weights w_b = exp2((G_b - G_max) log2(e) / lambda) in LDS (0 for a
+// non-finite G_b); then lane j < 4 * horizon owns element (t, c) = (j / 4, j % 4) and runs the two fp32 fma
+// chains over b ascending (every lane the same weight sum).  No finite return: branch 0's rows.
+#ifndef HG_MPPI_LDS_BRANCHES   // weights kept in LDS up to this many branches; past it they are recomputed
+#define HG_MPPI_LDS_BRANCHES 1024
+#endif
+__global__ __launch_bounds__(64) void mppi_update_kernel(const float* __restrict__ actions, const float* __restrict__ ret,
+                                                         int64_t n, uint32_t branches, int32_t horizon, float k,
+                                                         float* __restrict__ nominal) {
+    __shared__ float s_w[HG_MPPI_LDS_BRANCHES];
+    const int lane = threadIdx.x;
+    const int64_t e = blockIdx.x;
+    const float* G = ret + e * branches;
+    float gmax = -INFINITY;
+    for (uint32_t b = lane; b < branches; b += 64) {
+        const float g = G[b];
+        gmax = isfinite(g) ? fmaxf(gmax, g) : gmax;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) gmax = fmaxf(gmax, __shfl_xor(gmax, o));
+    const bool none = !(gmax > -INFINITY);   // (uniform) no finite return
+    auto weight = [&](uint32_t b) {
+        const float g = G[b];
+        return isfinite(g) ? exp2f((g - gmax) * k) : 0.f;
+    };
+    const bool in_lds = branches <= HG_MPPI_LDS_BRANCHES;   // (uniform)
+    if (in_lds && !none) {
+        for (uint32_t b = lane; b < branches; b += 64) s_w[b] = weight(b);
+    }
+    __syncthreads();
+    const int64_t rows = n * branches;
+    // four elements per lane at a time (j, j + 64, j + 128, j + 192): four independent chains whose loads
+    // are in flight together; each element's own chain is over b ascending whatever the grouping
+    const int nel = 4 * horizon;
+    for (int j0 = lane; j0 < nel; j0 += 256) {
+        const float* col[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int j = j0 + 64 * q < nel ? j0 + 64 * q : j0;   // (past the end: element j0 again, not stored)
+            col[q] = actions + ((int64_t)(j >> 2) * rows + e * branches) * 4 + (j & 3);
+        }
+        float num[4] = {0.f, 0.f, 0.f, 0.f}, den = 0.f;
+        if (!none) {
+#pragma unroll 4
+            for (uint32_t b = 0; b < branches; ++b) {
+                const float w = in_lds ? s_w[b] : weight(b);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) num[q] = fmaf(w, col[q][4 * (int64_t)b], num[q]);
+                den = den + w;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int j = j0 + 64 * q;
+            if (j < nel) nominal[((int64_t)(j >> 2) * n + e) * 4 + (j & 3)] = none ? col[q][0] : num[q] / den;
+        }
+    }
 }
 
 // reset_mode RETRIM with next-step auto-reset (hg_env::ov): one launch holds the trims of the previous
@@ -2026,6 +2214,44 @@ static void dispatch_rollout_policy(const hg_env* e, hipStream_t s, const StepAr
     }
 }
 
+// hg_rollout_branch's launch: task x noise mode x the constant-specialised step when the env uses it; the
+// lone-wave variant while the rows fit two waves per SIMD (its registers bound to the one or two waves the
+// rows make), else the bulk one (hg_rollout's rule on rows)
+template <int T>
+static void launch_rollout_branch(const hg_env* e, hipStream_t s, const StepArgs& a, const BranchArgs& br, int64_t rows,
+                                  bool noise_off) {
+    const unsigned grid = (unsigned)((rows + kStepBlock - 1) / kStepBlock);
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kStepBlock), 0, s, e->state, rows, (uint64_t)e->cfg.seed,
+                           (int64_t)e->cfg.env_offset, PARAM_ARG(e), e->tmpl_dev, a, br);
+    };
+    auto pick = [&](auto waves) {
+        constexpr int W = decltype(waves)::value;
+        if (e->baked) {
+            noise_off ? go(rollout_branch_kernel<T, true, W, true>) : go(rollout_branch_kernel<T, false, W, true>);
+        } else {   // (the generic step fits two waves per SIMD unbound: no WAVES 1 of it)
+            constexpr int WG = W < 2 ? 2 : W;
+            noise_off ? go(rollout_branch_kernel<T, true, WG, false>) : go(rollout_branch_kernel<T, false, WG, false>);
+        }
+    };
+    if (rows <= HG_NT_WAVES * e->resident_envs) {
+        ++e->n_launch[4];
+        if (rows <= e->resident_envs) pick(std::integral_constant<int, 1>{});
+        else pick(std::integral_constant<int, 2>{});
+    } else {
+        ++e->n_launch[5];
+        pick(std::integral_constant<int, 3>{});
+    }
+}
+static void dispatch_rollout_branch(const hg_env* e, hipStream_t s, const StepArgs& a, const BranchArgs& br, int64_t rows,
+                                    bool noise_off) {
+    switch (e->cfg.task) {
+        case HG_TASK_HOVER: launch_rollout_branch<HG_TASK_HOVER>(e, s, a, br, rows, noise_off); break;
+        case HG_TASK_FORWARD_FLIGHT: launch_rollout_branch<HG_TASK_FORWARD_FLIGHT>(e, s, a, br, rows, noise_off); break;
+        default: launch_rollout_branch<HG_TASK_HELI>(e, s, a, br, rows, noise_off); break;
+    }
+}
+
 // ov mode's launch: `ov_trim_blocks` trim blocks (the previous step's ends; blocks without a job exit at
 // once) ahead of the step's blocks -- never more than one per env (a step ends at most n episodes)
 #ifndef HG_OV_TB_DIV   // (A/B knob: the overlapped launch's trim blocks, n / 256 / this)
@@ -2818,6 +3044,109 @@ int32_t hg_gae(hg_env* e, const float* reward, const float* value, const float* 
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     hipLaunchKernelGGL(gae_kernel, dim3(grid_for(e->n)), dim3(kBlock), 0, (hipStream_t)stream, reward, value, next_value,
                        terminated, truncated, (int64_t)e->n, nsteps, gamma, lam, adv_out, ret_out);
+    HIP_TRY(hipGetLastError());
+    return HG_OK;
+}
+
+// The planning calls check their plain arguments before the handle, so that a bad one is refused with
+// its own message whatever the handle.  None of them touches the handle's chain or re-trim bookkeeping:
+// they read the env and leave it as it is.
+static int32_t branch_shape(const char* who, int32_t horizon, int32_t branches) {
+    if (horizon < 1) return fail(HG_E_INVALID, std::string(who) + ": horizon must be >= 1");
+    if (branches < 1) return fail(HG_E_INVALID, std::string(who) + ": branches must be >= 1");
+    return HG_OK;
+}
+static int32_t branch_rows(const char* who, const hg_env* e, int32_t branches, int64_t* rows) {
+    *rows = e->n * (int64_t)branches;
+    if (*rows >= (int64_t)INT32_MAX - 255)
+        return fail(HG_E_INVALID, std::string(who) + ": N * branches must be below 2^31 - 256");
+    return HG_OK;
+}
+
+int32_t hg_rollout_branch(hg_env* e, const float* actions, int32_t horizon, int32_t branches, float gamma,
+                          int32_t noise_mode, float* ret, int32_t* alive_steps, uint8_t* end_info, void* stream) {
+    if (branch_shape("hg_rollout_branch", horizon, branches) != HG_OK) return HG_E_INVALID;
+    if (!std::isfinite(gamma) || !(gamma > 0.f) || gamma > 1.f)
+        return fail(HG_E_INVALID, "hg_rollout_branch: gamma must be in (0, 1]");
+    if (noise_mode != HG_BRANCH_NOISE_ENV && noise_mode != HG_BRANCH_NOISE_OFF)
+        return fail(HG_E_INVALID, "hg_rollout_branch: noise_mode must be HG_BRANCH_NOISE_ENV or HG_BRANCH_NOISE_OFF");
+    if (!actions || !ret) return fail(HG_E_INVALID, "hg_rollout_branch: actions/return must be device pointers");
+    if ((uintptr_t)actions & 15) return fail(HG_E_INVALID, "hg_rollout_branch: actions must be 16-byte aligned");
+    if (((uintptr_t)ret & 3) || ((uintptr_t)alive_steps & 3))
+        return fail(HG_E_INVALID, "hg_rollout_branch: return and alive_steps must be 4-byte aligned");
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    int64_t rows = 0;
+    if (branch_rows("hg_rollout_branch", e, branches, &rows) != HG_OK) return HG_E_INVALID;
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    StepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.hmap = e->hmap;
+    a.actions = actions;
+    a.nsteps = horizon;
+    a.retrim_slot = -1;
+    BranchArgs br;
+    br.ret = ret;
+    br.alive_steps = alive_steps;
+    br.end_info = end_info;
+    br.branches = (uint32_t)branches;
+    br.gamma = gamma;
+    dispatch_rollout_branch(e, (hipStream_t)stream, a, br, rows, noise_mode == HG_BRANCH_NOISE_OFF);
+    HIP_TRY(hipGetLastError());
+    return HG_OK;
+}
+
+int32_t hg_mppi_sample(hg_env* e, const float* nominal, int32_t horizon, int32_t branches, const float sigma[4],
+                       const float lo[4], const float hi[4], uint64_t sample_seed, float* actions_out, void* stream) {
+    if (branch_shape("hg_mppi_sample", horizon, branches) != HG_OK) return HG_E_INVALID;
+    if (!sigma || !lo || !hi) return fail(HG_E_INVALID, "hg_mppi_sample: sigma/lo/hi must be host arrays of 4");
+    MppiBox box;
+    for (int c = 0; c < 4; ++c) {
+        if (!std::isfinite(sigma[c]) || sigma[c] < 0.f) return fail(HG_E_INVALID, "hg_mppi_sample: sigma must be finite and >= 0");
+        if (!(lo[c] <= hi[c])) return fail(HG_E_INVALID, "hg_mppi_sample: lo must be <= hi");
+        box.sigma[c] = sigma[c];
+        box.lo[c] = lo[c];
+        box.hi[c] = hi[c];
+    }
+    if (!nominal || !actions_out) return fail(HG_E_INVALID, "hg_mppi_sample: nominal/actions_out must be device pointers");
+    if (((uintptr_t)nominal & 15) || ((uintptr_t)actions_out & 15))
+        return fail(HG_E_INVALID, "hg_mppi_sample: nominal and actions_out must be 16-byte aligned");
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    int64_t rows = 0;
+    if (branch_rows("hg_mppi_sample", e, branches, &rows) != HG_OK) return HG_E_INVALID;
+    const int64_t blocks = (rows * horizon + kBlock - 1) / kBlock;
+    if (blocks > (int64_t)INT32_MAX) return fail(HG_E_INVALID, "hg_mppi_sample: horizon * N * branches too large");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    hipLaunchKernelGGL(mppi_sample_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4*>(nominal), (int64_t)e->n, (uint32_t)branches, horizon,
+                       (int64_t)e->cfg.env_offset, sample_seed, box, reinterpret_cast<float4*>(actions_out));
+    HIP_TRY(hipGetLastError());
+    return HG_OK;
+}
+
+int32_t hg_mppi_update(hg_env* e, const float* actions, const float* ret, int32_t horizon, int32_t branches, float lambda,
+                       float* nominal_out, void* stream) {
+    if (branch_shape("hg_mppi_update", horizon, branches) != HG_OK) return HG_E_INVALID;
+    const float k = (float)(1.4426950408889634 / (double)lambda);   // log2(e) / lambda
+    if (!std::isfinite(lambda) || !(lambda > 0.f) || !std::isfinite(k))
+        return fail(HG_E_INVALID, "hg_mppi_update: lambda must be > 0 (and log2(e) / lambda finite in fp32)");
+    if (!actions || !ret || !nominal_out)
+        return fail(HG_E_INVALID, "hg_mppi_update: actions/return/nominal_out must be device pointers");
+    if (((uintptr_t)actions & 3) || ((uintptr_t)ret & 3) || ((uintptr_t)nominal_out & 3))
+        return fail(HG_E_INVALID, "hg_mppi_update: actions, return and nominal_out must be 4-byte aligned");
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    int64_t rows = 0;
+    if (branch_rows("hg_mppi_update", e, branches, &rows) != HG_OK) return HG_E_INVALID;
+    {   // the candidates are read while the nominal is written
+        const uintptr_t a0 = (uintptr_t)actions, a1 = a0 + (uintptr_t)horizon * (uintptr_t)rows * 16;
+        const uintptr_t o0 = (uintptr_t)nominal_out, o1 = o0 + (uintptr_t)horizon * (uintptr_t)e->n * 16;
+        if (o0 < a1 && a0 < o1) return fail(HG_E_INVALID, "hg_mppi_update: nominal_out may not alias actions");
+    }
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    hipLaunchKernelGGL(mppi_update_kernel, dim3((unsigned)e->n), dim3(64), 0, (hipStream_t)stream, actions, ret,
+                       (int64_t)e->n, (uint32_t)branches, horizon, k, nominal_out);
     HIP_TRY(hipGetLastError());
     return HG_OK;
 }

@@ -25,6 +25,8 @@ HG_RESET_TEMPLATE, HG_RESET_RETRIM = 0, 1
 RESET_MODES = {"template": HG_RESET_TEMPLATE, "retrim": HG_RESET_RETRIM}
 HG_AUTORESET_SAME_STEP, HG_AUTORESET_NEXT_STEP = 0, 1
 AUTORESET_MODES = {"same_step": HG_AUTORESET_SAME_STEP, "next_step": HG_AUTORESET_NEXT_STEP}
+HG_BRANCH_NOISE_ENV, HG_BRANCH_NOISE_OFF = 0, 1
+BRANCH_NOISE_MODES = {"env": HG_BRANCH_NOISE_ENV, "off": HG_BRANCH_NOISE_OFF}
 HG_ABI_VERSION = 3
 
 AIRFRAME_FIELDS = (
@@ -110,6 +112,12 @@ _SIGS = {
     "hg_policy_eval": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P]),
     "hg_rollout_ac": (ctypes.c_int32, [_P, _P, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hg_gae": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_float, ctypes.c_float, _P, _P, _P]),
+    "hg_rollout_branch": (ctypes.c_int32, [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _P, _P,
+                                           _P, _P]),
+    "hg_mppi_sample": (ctypes.c_int32, [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float),
+                                        ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.c_uint64, _P,
+                                        _P]),
+    "hg_mppi_update": (ctypes.c_int32, [_P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _P, _P]),
     "hg_trim_batch": (ctypes.c_int32, [_P, _P, ctypes.c_int64, _P, _P, _P, _P, _P]),
     "hg_retrim_failures": (ctypes.c_int32, [_P, ctypes.POINTER(ctypes.c_int64)]),
     "hg_set_retrim_overlap": (ctypes.c_int32, [_P, ctypes.c_int32]),

@@ -1,0 +1,72 @@
+"""Sampling-based planning on the device: an MPPI controller over HeliVecEnv's branched rollouts.
+
+Every control step the planner perturbs a nominal action sequence per env (hg_mppi_sample), scores all
+candidates from the env's current state in one launch that does not touch the env (hg_rollout_branch),
+and averages them with softmax weights of their returns (hg_mppi_update).  All buffers are allocated
+once; a plan() is three kernel launches per iteration and no host synchronisation.
+"""
+import numpy as np
+
+
+class MPPI:
+    """Model-predictive path integral control of the N envs of `env` (a HeliVecEnv).
+
+    horizon: steps each candidate is rolled out; branches: candidates per env (branch 0 is always the
+    unperturbed nominal); sigma: the perturbation's standard deviation, lam: the softmax temperature
+    (in return units), lo / hi: the action bounds the candidates are clamped to -- each a scalar or 4
+    values.  gamma: the discount of the candidates' returns.  noise: "env" -- every candidate meets the
+    turbulence its env is about to draw, so the planner sees the gusts ahead -- or "off", a
+    certainty-equivalent planner.  seed: the perturbations' key; each sampling advances it by one.
+
+    The nominal starts at the env's trim action.  A control loop is
+        a = mppi.plan(); env.step(a); mppi.shift()
+    with mppi.reset(mask) for the envs whose episode ended.
+    """
+
+    def __init__(self, env, horizon, branches, sigma, lam, lo=-1.0, hi=1.0, gamma=1.0, noise="env", seed=0):
+        self.env = env
+        t = self.torch = env.torch
+        self.horizon, self.branches = int(horizon), int(branches)
+        if self.horizon < 1 or self.branches < 1:
+            raise ValueError("horizon and branches must be >= 1")
+        self.sigma, self.lam, self.lo, self.hi = sigma, float(lam), lo, hi
+        self.gamma, self.noise, self.seed = float(gamma), noise, int(seed)
+        N, H, B = env.num_envs, self.horizon, self.branches
+        self.trim_action = t.as_tensor(np.asarray(env.template()["action"], dtype=np.float32), device=env.device)
+        self.nominal = self.trim_action.expand(H, N, 4).contiguous()
+        self._next = t.empty_like(self.nominal)
+        self.actions = t.empty((H, N * B, 4), dtype=t.float32, device=env.device)
+        self.scores = None
+        self.samplings = 0
+
+    def plan(self, iterations=1):
+        """`iterations` rounds of sample -> rollout_branch -> update on the current stream.  Returns the
+        nominal's first action [N, 4] (a view: step the env with it before the next plan / shift)."""
+        env = self.env
+        for _ in range(int(iterations)):
+            env.mppi_sample(self.nominal, self.branches, self.sigma, self.lo, self.hi, self.seed + self.samplings,
+                            out=self.actions)
+            self.samplings += 1
+            self.scores = env.rollout_branch(self.actions, self.branches, gamma=self.gamma, noise=self.noise,
+                                             out=self.scores)
+            env.mppi_update(self.actions, self.scores["returns"], self.lam, out=self._next)
+            self.nominal, self._next = self._next, self.nominal
+        return self.nominal[0]
+
+    def shift(self):
+        """Advance the nominal by one step: row t takes row t + 1, the last row is repeated."""
+        if self.horizon > 1:
+            self._next[:-1].copy_(self.nominal[1:])
+            self._next[-1].copy_(self.nominal[-1])
+            self.nominal, self._next = self._next, self.nominal
+
+    def reset(self, mask=None):
+        """The nominal of the envs where `mask` != 0 (all envs if None) back to the trim action."""
+        if mask is None:
+            self.nominal.copy_(self.trim_action.expand_as(self.nominal))
+            return
+        t = self.torch
+        m = t.as_tensor(mask, device=self.nominal.device).reshape(-1) != 0
+        if m.shape[0] != self.nominal.shape[1]:
+            raise ValueError(f"mask must have {self.nominal.shape[1]} entries, got {m.shape[0]}")
+        self.nominal.copy_(t.where(m[None, :, None], self.trim_action.expand_as(self.nominal), self.nominal))

@@ -699,6 +699,104 @@ class HeliVecEnv(*_VEC_BASES):
                                     K, float(gamma), float(lam), p["advantages"], p["returns"], self._stream()))
         return out
 
+    # ------------------------------------------------------------------ branched planning rollouts
+    def _plan_tensor(self, x, shape, name, dtype=None):
+        """`x` as the library reads it: a contiguous tensor of `shape` and `dtype` on the env's device
+        (ValueError otherwise: nothing is converted, the kernels take the buffers as they are)."""
+        t = self.torch
+        dtype = t.float32 if dtype is None else dtype
+        if (not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device or not x.is_contiguous()
+                or tuple(x.shape) != tuple(shape)):
+            got = f"{tuple(x.shape)} {x.dtype} on {x.device}" if isinstance(x, t.Tensor) else type(x).__name__
+            raise ValueError(f"{name} must be a contiguous {dtype} {tuple(shape)} tensor on {self.device}, got {got}")
+        return x
+
+    @staticmethod
+    def _plan_count(v, name):
+        if isinstance(v, bool) or int(v) != v or int(v) < 1:
+            raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+        return int(v)
+
+    def rollout_branch(self, actions, branches, gamma=1.0, noise="env", out=None):
+        """Score `branches` candidate action sequences per env without touching the env
+        (hg_rollout_branch).  actions [H, N*branches, 4], row e * branches + b the branch b of env e.
+        Every branch starts from its env's current state and evolves as rollout() would, up to and
+        including its first terminated / truncated step, with no reset.  Returns a dict of device
+        tensors: returns [N, branches] float32 (sum of gamma^t reward_t), alive_steps [N, branches]
+        int32 (steps up to and including the ending one) and end_info [N, branches] uint8 (the ending
+        step's info bits, 0 for a branch that survived).  noise="env": every branch meets the
+        turbulence its env is about to draw (the planner sees the gusts ahead); "off": none.
+        `out`: a dict returned by a previous call with the same shapes, reused."""
+        t = self.torch
+        B, N = self._plan_count(branches, "branches"), self.num_envs
+        if not isinstance(actions, t.Tensor) or actions.ndim != 3 or actions.shape[0] < 1:
+            raise ValueError(f"actions must be a [H, {N * B}, 4] tensor")
+        H = int(actions.shape[0])
+        a = self._plan_tensor(actions, (H, N * B, _abi.HG_N_ACT), "actions")
+        if noise not in _abi.BRANCH_NOISE_MODES:
+            raise ValueError(f"noise must be one of {sorted(_abi.BRANCH_NOISE_MODES)}, got {noise!r}")
+        if out is None:
+            out = dict(returns=t.empty((N, B), dtype=t.float32, device=self.device),
+                       alive_steps=t.empty((N, B), dtype=t.int32, device=self.device),
+                       end_info=t.empty((N, B), dtype=t.uint8, device=self.device))
+        ret = self._plan_tensor(out["returns"], (N, B), "out['returns']")
+        alive = self._plan_tensor(out["alive_steps"], (N, B), "out['alive_steps']", t.int32)
+        end = self._plan_tensor(out["end_info"], (N, B), "out['end_info']", t.uint8)
+        self._keep_plan = a
+        self._check(self.lib.hg_rollout_branch(self._h, _ptr(a), H, B, float(gamma), _abi.BRANCH_NOISE_MODES[noise],
+                                               _ptr(ret), _ptr(alive), _ptr(end), self._stream()))
+        return out
+
+    @staticmethod
+    def _four(v, name):
+        a = np.asarray(v, dtype=np.float32).reshape(-1)
+        if a.size == 1:
+            a = np.repeat(a, 4)
+        if a.size != 4:
+            raise ValueError(f"{name} must be a scalar or 4 values, got {np.shape(v)}")
+        return (ctypes.c_float * 4)(*a.tolist())
+
+    def mppi_sample(self, nominal, branches, sigma, lo, hi, seed, out=None):
+        """Candidates around `nominal` [H, N, 4] (hg_mppi_sample): out [H, N*branches, 4] =
+        clamp(nominal + sigma * z, lo, hi) with z standard normals keyed by (global env id, t, branch)
+        and `seed` (vary it per control step); branch 0 is the clamped nominal itself.  sigma, lo, hi:
+        a scalar or 4 values each."""
+        t = self.torch
+        B, N = self._plan_count(branches, "branches"), self.num_envs
+        if not isinstance(nominal, t.Tensor) or nominal.ndim != 3 or nominal.shape[0] < 1:
+            raise ValueError(f"nominal must be a [H, {N}, 4] tensor")
+        H = int(nominal.shape[0])
+        m = self._plan_tensor(nominal, (H, N, _abi.HG_N_ACT), "nominal")
+        s, l, h = self._four(sigma, "sigma"), self._four(lo, "lo"), self._four(hi, "hi")
+        if out is None:
+            out = t.empty((H, N * B, _abi.HG_N_ACT), dtype=t.float32, device=self.device)
+        o = self._plan_tensor(out, (H, N * B, _abi.HG_N_ACT), "out")
+        self._keep_plan = m
+        self._check(self.lib.hg_mppi_sample(self._h, _ptr(m), H, B, s, l, h, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(o),
+                                            self._stream()))
+        return o
+
+    def mppi_update(self, actions, returns, lam, out=None):
+        """The MPPI update (hg_mppi_update): out [H, N, 4] = the candidates `actions` [H, N*branches, 4]
+        averaged per env with weights exp((G_b - G_max) / lam) of `returns` [N, branches]; a
+        non-finite return weighs 0, an env without a finite one keeps branch 0."""
+        t = self.torch
+        N = self.num_envs
+        if not isinstance(returns, t.Tensor) or returns.ndim != 2 or returns.shape[1] < 1:
+            raise ValueError(f"returns must be a [{N}, branches] tensor")
+        B = int(returns.shape[1])
+        g = self._plan_tensor(returns, (N, B), "returns")
+        if not isinstance(actions, t.Tensor) or actions.ndim != 3 or actions.shape[0] < 1:
+            raise ValueError(f"actions must be a [H, {N * B}, 4] tensor")
+        H = int(actions.shape[0])
+        a = self._plan_tensor(actions, (H, N * B, _abi.HG_N_ACT), "actions")
+        if out is None:
+            out = t.empty((H, N, _abi.HG_N_ACT), dtype=t.float32, device=self.device)
+        o = self._plan_tensor(out, (H, N, _abi.HG_N_ACT), "out")
+        self._keep_plan = (a, g)
+        self._check(self.lib.hg_mppi_update(self._h, _ptr(a), _ptr(g), H, B, float(lam), _ptr(o), self._stream()))
+        return o
+
     def trim_batch(self, wind_ned):
         """Device batched trim (hg_trim_batch) of this env's trim condition against each row of
         `wind_ned` [K,3] (ft/s NED): the reset the reference computes from its second episode on.

@@ -357,6 +357,64 @@ int32_t hg_gae(hg_env* env, const float* reward_dev, const float* value_dev, con
                const uint8_t* terminated_dev, const uint8_t* truncated_dev, int32_t nsteps, float gamma, float lam,
                float* adv_out_dev, float* ret_out_dev, void* stream);
 
+/* ---- Branched planning rollouts: many candidate action sequences per env, scored without touching it.
+ *
+ * What a receding-horizon sampling planner (MPPI, CEM, random shooting) needs from the rollout: `branches`
+ * candidates per env, all starting from the env's current state, each reduced to one discounted return.
+ * Row r = e * branches + b of every [N*branches] array is branch b of env e.  All three calls are
+ * asynchronous on `stream`, allocate nothing, can be captured into a graph, and do not modify the env:
+ * not its state, counters, azimuth records, the chain bookkeeping of hg_step_chained, nor the overlapped
+ * re-trim.  HG_E_INVALID (env untouched) for horizon < 1, branches < 1, N * branches >= 2^31 - 256, a
+ * NULL or misaligned pointer, and what each call names below.
+ *
+ * hg_rollout_branch: actions_dev [horizon, N*branches, 4] (16-byte aligned) -> return_dev [N*branches],
+ * alive_steps_dev [N*branches] i32 or NULL, end_info_dev [N*branches] u8 or NULL.
+ *   Branch b of env e starts from env e's state and counters exactly as the env's next hg_step would read
+ *   them and evolves exactly as hg_rollout would evolve that env under actions[t, r], up to and including
+ *   the first step whose terminated or truncated flag is set (failure, success, max_time,
+ *   max_episode_steps); after it the branch contributes nothing.  There is never a reset inside a
+ *   branch, whatever the handle's autoreset, autoreset_mode or reset_mode: HG_RESET_RETRIM handles are
+ *   accepted.  The branches of an env waiting for its next-step auto-reset (negative step counter: its
+ *   next step ignores the action) return 0 with alive_steps 0 and end_info 0.
+ *   return[r]      = sum over t < T_r of gamma^t reward_t, fp32, in step order: G = fma(disc, reward_t, G),
+ *                    then disc = disc * gamma, from G = 0, disc = 1;  gamma in (0, 1].
+ *   alive_steps[r] = T_r, the steps up to and including the ending one (horizon for a surviving branch).
+ *   end_info[r]    = the ending step's HG_INFO_* bits without HG_INFO_RESET; 0 for a surviving branch.
+ *   noise_mode HG_BRANCH_NOISE_ENV: the turbulence noise of env e's own key (env_offset + e, its episode
+ *     step and episode index): every branch of an env meets the realisation the env itself will meet.
+ *     These are common random numbers between the candidates, and they make the call bitwise hg_rollout
+ *     of that env.  Stated plainly: THIS PLANNER SEES THE GUSTS AHEAD -- its returns are those of the
+ *     noise the env is about to draw, which no real controller knows.
+ *   noise_mode HG_BRANCH_NOISE_OFF: eta = 0 through the same wind step, a certainty-equivalent planner;
+ *     bitwise hg_rollout with an all-zero eta_dev.
+ *   Counted by hg_debug_launches as a lone-wave launch while N * branches rows fit two waves per SIMD,
+ *   as a bulk launch past that. */
+enum { HG_BRANCH_NOISE_ENV = 0, HG_BRANCH_NOISE_OFF = 1 };
+
+int32_t hg_rollout_branch(hg_env* env, const float* actions_dev, int32_t horizon, int32_t branches, float gamma,
+                          int32_t noise_mode, float* return_dev, int32_t* alive_steps_dev, uint8_t* end_info_dev,
+                          void* stream);
+
+/* Candidates around a nominal sequence nominal_dev [horizon, N, 4] -> actions_out_dev [horizon, N*branches, 4]
+ * (both 16-byte aligned):   actions_out[t, r, c] = clamp(nominal[t, e, c] + sigma[c] * z_c, lo[c], hi[c]),
+ * the sum one fma.  Branch 0 has no perturbation: it is the clamped nominal.  z is four standard normals
+ * from ONE Philox4x32-10 call with counter (gid_lo, gid_hi, t, b), gid = env_offset + e, and key
+ * (sample_seed_lo, sample_seed_hi), through the Box-Muller of the policy noise above (same device
+ * functions).  Keyed by the global env id: the rows do not depend on how the envs are sharded.  The
+ * caller varies sample_seed per control step.  sigma (finite, >= 0), lo <= hi: host arrays of 4, passed
+ * by value into the kernel's arguments. */
+int32_t hg_mppi_sample(hg_env* env, const float* nominal_dev, int32_t horizon, int32_t branches, const float sigma[4],
+                       const float lo[4], const float hi[4], uint64_t sample_seed, float* actions_out_dev,
+                       void* stream);
+
+/* The MPPI update, per env:   w_b = exp2((G_b - G_max) * (log2(e) / lambda)),  G_max the largest finite return,
+ *   nominal_out[t, e, c] = (sum_b w_b actions[t, r, c]) / (sum_b w_b),
+ * both sums fp32 fma chains over b ascending, so the result does not depend on N, on the env's position
+ * or on the launch shape.  A non-finite G_b gets weight 0; an env with no finite return gets branch 0's
+ * rows.  lambda > 0.  nominal_out_dev [horizon, N, 4] may not overlap actions_dev. */
+int32_t hg_mppi_update(hg_env* env, const float* actions_dev, const float* return_dev, int32_t horizon,
+                       int32_t branches, float lambda, float* nominal_out_dev, void* stream);
+
 /* Batched device trim:HelicopterDynamics.trim (helicopter_dynamics.py:491-576) of the env's trim
  * condition against `count` winds at once — the reset path of reset_mode HG_RESET_RETRIM, exposed
  * for direct use.  Same Newton iteration as hg_trim (fp64, trial point rounded to fp32), with the
@@ -415,7 +473,7 @@ int32_t hg_debug_queues(hg_env* env, int32_t* out);
  * hg_step_chained, hg_step_rows), out[1] steps whose launch held the previous step's re-trims
  * (hg_set_retrim_overlap), out[2] run-time specialised kernel launches, out[3] small-batch helper
  * kernel launches, out[4] lone-wave (one or two waves per SIMD) launches, out[5] bulk launches
- * (out[3..5] count hg_rollout's too).  Host only. */
+ * (out[3..5] count hg_rollout's too, out[4..5] hg_rollout_branch's).  Host only. */
 int32_t hg_debug_launches(const hg_env* env, int64_t* out);
 
 /* HG_RESET_RETRIM with next-step auto-reset (gymnasium's default, make_vec's): the episodes a step ends
