@@ -26,6 +26,7 @@
 #include "physics.h"
 #include "trim.h"
 #include "retrim.h"
+#include "ppo_grad.h"
 #include "retrim_body.h"
 #include "baked.h"
 
@@ -3045,6 +3046,53 @@ int32_t hg_gae(hg_env* e, const float* reward, const float* value, const float* 
     hipLaunchKernelGGL(gae_kernel, dim3(grid_for(e->n)), dim3(kBlock), 0, (hipStream_t)stream, reward, value, next_value,
                        terminated, truncated, (int64_t)e->n, nsteps, gamma, lam, adv_out, ret_out);
     HIP_TRY(hipGetLastError());
+    return HG_OK;
+}
+
+int64_t hg_ppo_grad_workspace_bytes(void) { return hgk::kPpoWorkspaceBytes; }
+
+int32_t hg_ppo_grad(hg_env* e, const float* theta, const float* obs_mean, const float* obs_scale, const float* obs,
+                    const float* actions, const float* logp_old, const float* adv, const float* ret, int64_t B,
+                    const int32_t* index, int64_t M, float clip, float vf_coef, float ent_coef, float* grad, float* stats,
+                    void* workspace, void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!theta || !obs || !actions || !logp_old || !adv || !ret || !grad || !workspace)
+        return fail(HG_E_INVALID,
+                    "hg_ppo_grad: theta/obs/actions/logp_old/adv/ret/grad/workspace must be device pointers");
+    if (((uintptr_t)actions & 15) || ((uintptr_t)workspace & 15))
+        return fail(HG_E_INVALID, "hg_ppo_grad: actions and workspace must be 16-byte aligned");
+    if ((((uintptr_t)theta | (uintptr_t)obs_mean | (uintptr_t)obs_scale | (uintptr_t)obs | (uintptr_t)logp_old |
+          (uintptr_t)adv | (uintptr_t)ret | (uintptr_t)index | (uintptr_t)grad | (uintptr_t)stats) & 3) != 0)
+        return fail(HG_E_INVALID, "hg_ppo_grad: every pointer must be 4-byte aligned");
+    if (B < 1) return fail(HG_E_INVALID, "hg_ppo_grad: B must be >= 1");
+    if (M < 1) return fail(HG_E_INVALID, "hg_ppo_grad: M must be >= 1");
+    if (M > (int64_t)INT32_MAX - 255) return fail(HG_E_INVALID, "hg_ppo_grad: M must be at most 2^31 - 256");
+    if (!index && M != B) return fail(HG_E_INVALID, "hg_ppo_grad: without an index M must equal B");
+    if (!(clip > 0.f) || !(clip < 1.f)) return fail(HG_E_INVALID, "hg_ppo_grad: clip must be in (0, 1)");
+    if (!std::isfinite(vf_coef) || vf_coef < 0.f || !std::isfinite(ent_coef) || ent_coef < 0.f)
+        return fail(HG_E_INVALID, "hg_ppo_grad: vf_coef and ent_coef must be finite and >= 0");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    hgk::PpoGradArgs a;
+    a.theta = theta;
+    a.mean = obs_mean;
+    a.scale = obs_scale;
+    a.obs = obs;
+    a.act = actions;
+    a.logp_old = logp_old;
+    a.adv = adv;
+    a.ret = ret;
+    a.index = index;
+    a.B = B;
+    a.M = M;
+    a.clip = clip;
+    a.vf_coef = vf_coef;
+    a.ent_coef = ent_coef;
+    a.inv_m = 1.0f / (float)M;
+    a.grad = grad;
+    a.stats = stats;
+    a.ws = (float*)workspace;
+    HIP_TRY(hgk::launch_ppo_grad(a, (hipStream_t)stream));
     return HG_OK;
 }
 

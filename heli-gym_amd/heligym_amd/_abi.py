@@ -28,6 +28,7 @@ AUTORESET_MODES = {"same_step": HG_AUTORESET_SAME_STEP, "next_step": HG_AUTORESE
 HG_BRANCH_NOISE_ENV, HG_BRANCH_NOISE_OFF = 0, 1
 BRANCH_NOISE_MODES = {"env": HG_BRANCH_NOISE_ENV, "off": HG_BRANCH_NOISE_OFF}
 HG_ABI_VERSION = 3
+HG_PPO_N_PARAMS = 5641
 
 AIRFRAME_FIELDS = (
     ["env_R", "env_T0", "env_LAPSE", "env_RO_SEA", "env_GRAV", "env_MAX_GR_ALT", "env_NS_MAX",
@@ -112,6 +113,9 @@ _SIGS = {
     "hg_policy_eval": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P]),
     "hg_rollout_ac": (ctypes.c_int32, [_P, _P, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hg_gae": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_float, ctypes.c_float, _P, _P, _P]),
+    "hg_ppo_grad_workspace_bytes": (ctypes.c_int64, []),
+    "hg_ppo_grad": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_float,
+                                     ctypes.c_float, ctypes.c_float, _P, _P, _P, _P]),
     "hg_rollout_branch": (ctypes.c_int32, [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _P, _P,
                                            _P, _P]),
     "hg_mppi_sample": (ctypes.c_int32, [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float),

@@ -90,3 +90,114 @@ def pack_value_head(head):
     if w.dtype != torch.float32 or b.dtype != torch.float32:
         raise ValueError(f"value head: w {tuple(w.shape)} / b {tuple(b.shape)} must be float32, got {w.dtype} / {b.dtype}")
     return w.detach().reshape(N_HIDDEN).contiguous(), b.detach().contiguous()
+
+
+# ---- the learner's side: one flat parameter vector and the clipped PPO loss (hg_ppo_grad)
+# name -> (offset, shape) in the flat vector theta [5641], in include/heligym_amd.h's order
+PPO_LAYOUT = {
+    "W1": (0, (N_HIDDEN, N_OBS)), "b1": (1088, (N_HIDDEN,)),
+    "W2": (1152, (N_HIDDEN, N_HIDDEN)), "b2": (5248, (N_HIDDEN,)),
+    "W3": (5312, (N_ACT, N_HIDDEN)), "b3": (5568, (N_ACT,)),
+    "log_std": (5572, (N_ACT,)),
+    "w_v": (5576, (N_HIDDEN,)), "b_v": (5640, (1,)),
+}
+PPO_N_PARAMS = 5641
+LOG_2PI = 1.8378770664093453   # ln(2 pi)
+
+
+def _count(shape):
+    n = 1
+    for s in shape:
+        n *= s
+    return n
+
+
+def ppo_views(flat):
+    """{name: view of `flat` [5641] with the tensor's shape} in PPO_LAYOUT's order (views, no copies)."""
+    if tuple(flat.shape) != (PPO_N_PARAMS,):
+        raise ValueError(f"the flat parameter vector must have shape ({PPO_N_PARAMS},), got {tuple(flat.shape)}")
+    return {k: flat[off:off + _count(shape)].view(shape) for k, (off, shape) in PPO_LAYOUT.items()}
+
+
+class ActorCriticParams:
+    """The actor nn.Sequential(Linear(17, 64), Tanh, Linear(64, 64), Tanh, Linear(64, 4)), the critic head
+    nn.Linear(64, 1) on its trunk and log_std (an nn.Parameter or tensor of shape [4]) as ONE flat float32
+    vector `theta` [5641] in hg_ppo_grad's layout, with one flat `grad` [5641] beside it.
+
+    Every parameter's .data is re-pointed at its view of `theta` and its .grad at its view of `grad`, so a
+    torch optimiser built on `parameters()` updates `theta` in place from what `HeliVecEnv.ppo_grad` wrote
+    into `grad`, and `env.set_policy(actor, log_std=...)` / `env.set_value_head(critic)` keep working on the
+    same modules.  (Do not call optimizer.zero_grad(): its default drops the .grad views, and ppo_grad
+    overwrites `grad` anyway.)  Pure torch, runs on the CPU; the modules are validated by pack_policy / pack_value_head
+    (ValueError for anything but the fixed fp32 model)."""
+
+    def __init__(self, actor, critic, log_std):
+        import torch
+        nn = torch.nn
+        pack_policy(actor, log_std=log_std.detach() if isinstance(log_std, torch.Tensor) else log_std)
+        pack_value_head(critic)
+        if not isinstance(actor, nn.Module) or not isinstance(critic, nn.Module):
+            raise ValueError("ActorCriticParams needs the actor and the critic as torch modules (their parameters are "
+                             "re-pointed at the flat vector)")
+        if log_std is None:
+            raise ValueError("log_std must be float32 of shape (4,), got None")
+        if not isinstance(log_std, nn.Parameter):
+            log_std = nn.Parameter(torch.as_tensor(log_std).detach().clone())
+        self.actor, self.critic, self.log_std = actor, critic, log_std
+        named = {"W1": actor[0].weight, "b1": actor[0].bias, "W2": actor[2].weight, "b2": actor[2].bias,
+                 "W3": actor[4].weight, "b3": actor[4].bias, "log_std": log_std, "w_v": critic.weight,
+                 "b_v": critic.bias}
+        device = actor[0].weight.device
+        for k, p in named.items():
+            if p.device != device:
+                raise ValueError(f"{k} lives on {p.device}, the actor on {device}")
+        self.theta = torch.empty((PPO_N_PARAMS,), dtype=torch.float32, device=device)
+        self.grad = torch.zeros((PPO_N_PARAMS,), dtype=torch.float32, device=device)
+        tv, gv = ppo_views(self.theta), ppo_views(self.grad)
+        self._named = named
+        with torch.no_grad():
+            for k, p in named.items():
+                tv[k].copy_(p.detach().reshape(tv[k].shape))
+                p.data = tv[k].view(p.shape)
+                p.grad = gv[k].view(p.shape)
+
+    def parameters(self):
+        """The nine parameters in the flat vector's order (what an optimiser takes)."""
+        return [self._named[k] for k in PPO_LAYOUT]
+
+    def views(self):
+        """{name: view of theta} in PPO_LAYOUT's order."""
+        return ppo_views(self.theta)
+
+
+def ppo_loss(theta_or_params, obs, actions, logp_old, adv, ret, clip, vf_coef, ent_coef, obs_mean=None,
+             obs_scale=None):
+    """The clipped PPO loss hg_ppo_grad differentiates (include/heligym_amd.h), in plain torch and in the
+    dtype of `theta` (an ActorCriticParams, or a flat [5641] tensor in PPO_LAYOUT's order, which may
+    require grad).  obs [M,17], actions [M,4], logp_old / adv / ret [M]: the minibatch's rows.  Returns
+    (L, stats) with stats the eight values of hg_ppo_grad's stats (index 7, the skipped entries, is 0)."""
+    import torch
+    theta = theta_or_params.theta if isinstance(theta_or_params, ActorCriticParams) else theta_or_params
+    p = ppo_views(theta)
+    x = obs
+    if obs_mean is not None:
+        x = x - obs_mean
+    if obs_scale is not None:
+        x = x * obs_scale
+    h1 = torch.tanh(x @ p["W1"].T + p["b1"])
+    h2 = torch.tanh(h1 @ p["W2"].T + p["b2"])
+    mu = h2 @ p["W3"].T + p["b3"]
+    v = h2 @ p["w_v"] + p["b_v"]
+    ls = p["log_std"]
+    z = (actions - mu) * torch.exp(-ls)
+    logp = -0.5 * (z * z).sum(-1) - ls.sum() - 2.0 * LOG_2PI
+    r = torch.exp(logp - logp_old)
+    pol = -torch.minimum(r * adv, torch.clamp(r, 1.0 - clip, 1.0 + clip) * adv)
+    val = 0.5 * (v - ret) ** 2
+    H = ls.sum() + 2.0 * (1.0 + LOG_2PI)
+    L = (pol + vf_coef * val).mean() - ent_coef * H
+    with torch.no_grad():
+        out = ((r < 1.0 - clip) | (r > 1.0 + clip)).to(theta.dtype).mean()
+        stats = torch.stack([pol.mean(), val.mean(), (logp_old - logp).mean(), out, H.detach(), L.detach(), r.mean(),
+                             torch.zeros((), dtype=theta.dtype, device=theta.device)])
+    return L, stats

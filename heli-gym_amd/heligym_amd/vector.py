@@ -699,6 +699,64 @@ class HeliVecEnv(*_VEC_BASES):
                                     K, float(gamma), float(lam), p["advantages"], p["returns"], self._stream()))
         return out
 
+    # ------------------------------------------------------------------ the PPO update's gradient
+    def _ppo_tensor(self, x, shape, name, dtype=None):
+        t = self.torch
+        dtype = t.float32 if dtype is None else dtype
+        if (not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device or not x.is_contiguous()
+                or tuple(x.shape) != tuple(shape)):
+            got = f"{tuple(x.shape)} {x.dtype} on {x.device}" if isinstance(x, t.Tensor) else type(x).__name__
+            raise ValueError(f"ppo_grad: {name} must be a contiguous {dtype} {tuple(shape)} tensor on {self.device}, "
+                             f"got {got}")
+        return x
+
+    def ppo_grad(self, params, obs, actions, logp_old, adv, ret, index=None, clip=0.2, vf_coef=1.0, ent_coef=0.0,
+                 obs_mean=None, obs_scale=None, stats=None):
+        """The clipped PPO loss's gradient over a minibatch in one kernel (hg_ppo_grad; the loss is
+        heligym_amd.policy.ppo_loss).  params: an ActorCriticParams on this device (its `theta` is read,
+        its `grad` overwritten).  obs [B,17], actions [B,4], logp_old / adv / ret [B]: the stored rows
+        (rollout_actor_critic's outputs, flattened; leading dimensions are merged), contiguous float32 on
+        the env's device.  index: int32 [M] rows of the minibatch (entries outside [0, B) are skipped and
+        counted in stats[7]), or None for all B rows in order.  obs_mean / obs_scale [17]: the policy's
+        input normalisation.  Returns (params.grad, stats [8]: policy term, value term, approximate KL,
+        clip fraction, entropy, loss, mean ratio, skipped entries); `stats`: a float32 [8] tensor to reuse.
+        Asynchronous on the current stream, allocates nothing after the first call, capturable; the env
+        is not modified."""
+        t = self.torch
+        theta = self._ppo_tensor(getattr(params, "theta", None), (_abi.HG_PPO_N_PARAMS,), "params.theta")
+        grad = self._ppo_tensor(getattr(params, "grad", None), (_abi.HG_PPO_N_PARAMS,), "params.grad")
+        if not isinstance(obs, t.Tensor) or obs.ndim < 2 or obs.shape[-1] != _abi.HG_N_OBS:
+            raise ValueError("ppo_grad: obs must be a [..., 17] tensor")
+        B = int(obs.numel() // _abi.HG_N_OBS)
+        if B < 1:
+            raise ValueError("ppo_grad: obs has no rows")
+        lead = tuple(obs.shape[:-1])
+        o = self._ppo_tensor(obs, lead + (_abi.HG_N_OBS,), "obs")
+        a = self._ppo_tensor(actions, lead + (_abi.HG_N_ACT,), "actions")
+        lp = self._ppo_tensor(logp_old, lead, "logp_old")
+        ad = self._ppo_tensor(adv, lead, "adv")
+        rt = self._ppo_tensor(ret, lead, "ret")
+        M, ix = B, None
+        if index is not None:
+            if not isinstance(index, t.Tensor) or index.ndim != 1 or index.shape[0] < 1:
+                raise ValueError("ppo_grad: index must be a non-empty int32 [M] tensor")
+            M = int(index.shape[0])
+            ix = self._ppo_tensor(index, (M,), "index", t.int32)
+        mean = None if obs_mean is None else self._ppo_tensor(obs_mean, (_abi.HG_N_OBS,), "obs_mean")
+        scale = None if obs_scale is None else self._ppo_tensor(obs_scale, (_abi.HG_N_OBS,), "obs_scale")
+        if stats is None:
+            stats = t.empty((8,), dtype=t.float32, device=self.device)
+        st = self._ppo_tensor(stats, (8,), "stats")
+        ws = getattr(self, "_ppo_workspace", None)
+        if ws is None:
+            ws = self._ppo_workspace = t.empty((int(self.lib.hg_ppo_grad_workspace_bytes()),), dtype=t.uint8,
+                                               device=self.device)
+        self._keep_ppo = (theta, o, a, lp, ad, rt, ix, mean, scale)
+        self._check(self.lib.hg_ppo_grad(self._h, _ptr(theta), _ptr(mean), _ptr(scale), _ptr(o), _ptr(a), _ptr(lp),
+                                         _ptr(ad), _ptr(rt), B, _ptr(ix), M, float(clip), float(vf_coef),
+                                         float(ent_coef), _ptr(grad), _ptr(st), _ptr(ws), self._stream()))
+        return grad, st
+
     # ------------------------------------------------------------------ branched planning rollouts
     def _plan_tensor(self, x, shape, name, dtype=None):
         """`x` as the library reads it: a contiguous tensor of `shape` and `dtype` on the env's device

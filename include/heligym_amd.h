@@ -357,6 +357,59 @@ int32_t hg_gae(hg_env* env, const float* reward_dev, const float* value_dev, con
                const uint8_t* terminated_dev, const uint8_t* truncated_dev, int32_t nsteps, float gamma, float lam,
                float* adv_out_dev, float* ret_out_dev, void* stream);
 
+/* ---- The update half: the clipped PPO loss's gradient for the actor-critic above, in one kernel.
+ *
+ * Flat parameter vector theta [HG_PPO_N_PARAMS] fp32, each tensor row-major [out,in] as torch.nn.Linear
+ * stores it (offset: tensor, count):
+ *      0: W1 [64,17] 1088     1088: b1 [64] 64      1152: W2 [64,64] 4096     5248: b2 [64] 64
+ *   5312: W3 [4,64] 256       5568: b3 [4] 4        5572: log_std [4] 4
+ *   5576: w_v [64] 64         5640: b_v [1] 1
+ * The call takes these raw weights, the LEARNER's current ones, not the handle's packed policy image:
+ * the weights change with every optimiser step inside an epoch, hg_set_policy is called once per
+ * collection.  `env` is used only for its device and the error convention (hg_last_error), as in hg_gae;
+ * the env is not modified: not its state, counters, azimuth records, the chain bookkeeping of
+ * hg_step_chained, nor the overlapped re-trim.
+ *
+ * The function.  Rows i of the minibatch: index_dev[0..M) into the B stored rows, or, with index_dev
+ * NULL, the rows 0..B-1 themselves (then M == B):
+ *   x = (obs_i - mean) * scale;  h1 = tanh(W1 x + b1);  h2 = tanh(W2 h1 + b2);  mu = W3 h2 + b3;  v = w_v . h2 + b_v
+ *   z = (a_i - mu) * exp(-log_std);   logp = -1/2 sum z^2 - sum log_std - 2 ln(2 pi);   r = exp(logp - logp_old_i)
+ *   L = (1/M) sum_i [ -min(r A_i, clamp(r, 1 - clip, 1 + clip) A_i) + vf_coef * 1/2 (v - ret_i)^2 ] - ent_coef * H,
+ *   H = sum log_std + 2 (1 + ln(2 pi))
+ * grad_dev [HG_PPO_N_PARAMS] = dL/dtheta in theta's layout, as torch autograd differentiates that
+ * expression: a sample contributes nothing through r when (A_i > 0 and r > 1 + clip) or (A_i < 0 and
+ * r < 1 - clip), and -A_i r dlogp otherwise.  grad_dev is overwritten, not accumulated into.
+ * Numerics: fp32 throughout; tanh is the policy's formula above and tanh' = 1 - h^2; every matrix
+ * product, forward and backward, is an exact fp32 fma chain on the fp32 matrix instruction (the biases
+ * the last k pair of the forward chains, as in the rollout kernels); the sums over samples are fp32.
+ * stats_dev [8] or NULL:  [0] mean policy term  [1] mean 1/2 (v - ret)^2, unweighted
+ *   [2] mean (logp_old - logp), the usual approximate KL  [3] fraction of samples with r outside
+ *   [1 - clip, 1 + clip]  [4] H  [5] L  [6] mean r  [7] skipped index entries, as a float.
+ * Out-of-range index entries (outside [0, B)) are skipped and counted, never dereferenced; the means
+ * still divide by M (1/M is a kernel argument).
+ * Asynchronous on `stream`, allocates nothing, capturable; theta_dev is read when the kernel runs, so a
+ * replayed graph sees updated weights.  Deterministic: no floating-point atomics; per-block partial sums
+ * go to workspace_dev (hg_ppo_grad_workspace_bytes() bytes, 16-byte aligned, contents irrelevant before
+ * and after) and are added in a fixed order, and the launch shape depends on M and compile-time constants
+ * only: two calls on the same inputs give the same bits.
+ * HG_E_INVALID, outputs untouched: NULL env; a NULL or misaligned (4 bytes; actions_dev and
+ * workspace_dev 16) required pointer; B < 1; M < 1; M > 2^31 - 256; index_dev NULL with M != B; clip not
+ * in (0, 1); a non-finite or negative vf_coef or ent_coef.  obs_mean_dev / obs_scale_dev [17] or NULL
+ * (0 / 1) are constants of the function, not differentiated. */
+#define HG_PPO_N_PARAMS 5641
+
+int64_t hg_ppo_grad_workspace_bytes(void);      /* fixed; a multiple of 16; host only */
+
+int32_t hg_ppo_grad(hg_env* env, const float* theta_dev,           /* [5641] the LEARNER's current weights */
+                    const float* obs_mean_dev, const float* obs_scale_dev,   /* [17] or NULL (0 / 1); constants */
+                    const float* obs_dev, const float* actions_dev,          /* [B,17], [B,4] (16-byte aligned) */
+                    const float* logp_old_dev, const float* adv_dev, const float* ret_dev,   /* [B] */
+                    int64_t B, const int32_t* index_dev, int64_t M,           /* minibatch rows, or NULL: M == B, rows 0..B-1 */
+                    float clip, float vf_coef, float ent_coef,
+                    float* grad_dev,      /* [5641] out, overwritten (not accumulated) */
+                    float* stats_dev,     /* [8] out or NULL */
+                    void* workspace_dev, void* stream);
+
 /* ---- Branched planning rollouts: many candidate action sequences per env, scored without touching it.
  *
  * What a receding-horizon sampling planner (MPPI, CEM, random shooting) needs from the rollout: `branches`
