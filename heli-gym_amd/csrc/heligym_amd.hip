@@ -27,6 +27,7 @@
 #include "trim.h"
 #include "retrim.h"
 #include "ppo_grad.h"
+#include "ppo_opt.h"
 #include "retrim_body.h"
 #include "baked.h"
 
@@ -1449,6 +1450,34 @@ __global__ __launch_bounds__(kBlock) void random_actions_kernel(float* act, int6
     const float w = hi - lo;
     reinterpret_cast<float4*>(act)[i] =
         make_float4(lo + w * u01(r.x), lo + w * u01(r.y), lo + w * u01(r.z), lo + w * u01(r.w));
+}
+
+// hg_ppo_shuffle: index[i] = the image of i under a keyed permutation of 0 .. B-1, one lane per element, no
+// sort and no scratch.  A balanced Feistel network of four rounds on 2 * half bits (half = ceil(w / 2), w the
+// bits of B - 1) permutes [0, 4^half), a domain under 4 B; values outside [0, B) are walked on through the
+// same permutation until they land inside, which they do because the orbit of i returns to i < B: the trip
+// count is bounded by the data, nothing waits on memory.  Round function: word 0 of Philox on the counter
+// (R, round, epoch) under the seed's key (tests/ppo_shuffle_ref.py restates it).
+__global__ __launch_bounds__(kBlock) void ppo_shuffle_kernel(int32_t* __restrict__ out, uint32_t B, uint32_t k0,
+                                                             uint32_t k1, int64_t epoch,
+                                                             const int32_t* __restrict__ epoch_dev, int half) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= (int64_t)B) return;
+    const uint64_t e = (uint64_t)(epoch + (epoch_dev ? (int64_t)epoch_dev[0] : 0));
+    const uint32_t e_lo = (uint32_t)e, e_hi = (uint32_t)(e >> 32), mask = (1u << half) - 1u;
+    uint32_t x = (uint32_t)i;
+    do {
+        uint32_t L = x >> half, R = x & mask;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t f = philox(U4{R, j, e_lo, e_hi}, k0, k1).x;
+            const uint32_t t = L ^ (f & mask);
+            L = R;
+            R = t;
+        }
+        x = (L << half) | R;
+    } while (x >= B);
+    out[i] = (int32_t)x;
 }
 
 // hg_debug_eta: the turbulence noise each env's next in-kernel step draws (wind_dynamics.py:49-52), from
@@ -3051,10 +3080,11 @@ int32_t hg_gae(hg_env* e, const float* reward, const float* value, const float* 
 
 int64_t hg_ppo_grad_workspace_bytes(void) { return hgk::kPpoWorkspaceBytes; }
 
-int32_t hg_ppo_grad(hg_env* e, const float* theta, const float* obs_mean, const float* obs_scale, const float* obs,
-                    const float* actions, const float* logp_old, const float* adv, const float* ret, int64_t B,
-                    const int32_t* index, int64_t M, float clip, float vf_coef, float ent_coef, float* grad, float* stats,
-                    void* workspace, void* stream) {
+// hg_ppo_grad's argument checks (hg_ppo_update makes them for all its minibatches before it enqueues anything)
+static int32_t ppo_grad_check(const hg_env* e, const float* theta, const float* obs_mean, const float* obs_scale,
+                              const float* obs, const float* actions, const float* logp_old, const float* adv,
+                              const float* ret, int64_t B, const int32_t* index, int64_t M, float clip, float vf_coef,
+                              float ent_coef, const float* grad, const float* stats, const void* workspace) {
     if (!e) return fail(HG_E_INVALID, "env is NULL");
     if (!theta || !obs || !actions || !logp_old || !adv || !ret || !grad || !workspace)
         return fail(HG_E_INVALID,
@@ -3071,6 +3101,16 @@ int32_t hg_ppo_grad(hg_env* e, const float* theta, const float* obs_mean, const 
     if (!(clip > 0.f) || !(clip < 1.f)) return fail(HG_E_INVALID, "hg_ppo_grad: clip must be in (0, 1)");
     if (!std::isfinite(vf_coef) || vf_coef < 0.f || !std::isfinite(ent_coef) || ent_coef < 0.f)
         return fail(HG_E_INVALID, "hg_ppo_grad: vf_coef and ent_coef must be finite and >= 0");
+    return HG_OK;
+}
+
+int32_t hg_ppo_grad(hg_env* e, const float* theta, const float* obs_mean, const float* obs_scale, const float* obs,
+                    const float* actions, const float* logp_old, const float* adv, const float* ret, int64_t B,
+                    const int32_t* index, int64_t M, float clip, float vf_coef, float ent_coef, float* grad, float* stats,
+                    void* workspace, void* stream) {
+    const int32_t rc = ppo_grad_check(e, theta, obs_mean, obs_scale, obs, actions, logp_old, adv, ret, B, index, M, clip,
+                                      vf_coef, ent_coef, grad, stats, workspace);
+    if (rc != HG_OK) return rc;
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     hgk::PpoGradArgs a;
@@ -3094,6 +3134,150 @@ int32_t hg_ppo_grad(hg_env* e, const float* theta, const float* obs_mean, const 
     a.ws = (float*)workspace;
     HIP_TRY(hgk::launch_ppo_grad(a, (hipStream_t)stream));
     return HG_OK;
+}
+
+// ---- the update phase on the device: optimiser state, shuffle, optimiser step, and the whole of it in one call
+int64_t hg_ppo_opt_state_bytes(void) { return hgk::kPpoOptStateBytes; }
+
+static int32_t ppo_state_check(const char* who, const hg_env* e, const void* state) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!state) return fail(HG_E_INVALID, std::string(who) + ": state must be a device pointer");
+    if ((uintptr_t)state & 15) return fail(HG_E_INVALID, std::string(who) + ": state must be 16-byte aligned");
+    return HG_OK;
+}
+
+int32_t hg_ppo_opt_init(hg_env* e, void* state, void* stream) {
+    const int32_t rc = ppo_state_check("hg_ppo_opt_init", e, state);
+    if (rc != HG_OK) return rc;
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    HIP_TRY(hgk::launch_ppo_opt_zero((uint32_t*)state, (hipStream_t)stream));
+    return HG_OK;
+}
+
+static int32_t ppo_shuffle_check(const hg_env* e, int64_t B, const int32_t* epoch_dev, const int32_t* index_out) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!index_out) return fail(HG_E_INVALID, "hg_ppo_shuffle: index_out must be a device pointer");
+    if ((((uintptr_t)index_out | (uintptr_t)epoch_dev) & 3) != 0)
+        return fail(HG_E_INVALID, "hg_ppo_shuffle: index_out and epoch_dev must be 4-byte aligned");
+    if (B < 1) return fail(HG_E_INVALID, "hg_ppo_shuffle: B must be >= 1");
+    if (B > (int64_t)INT32_MAX - 255) return fail(HG_E_INVALID, "hg_ppo_shuffle: B must be at most 2^31 - 256");
+    return HG_OK;
+}
+
+int32_t hg_ppo_shuffle(hg_env* e, int64_t B, uint64_t seed, int64_t epoch, const int32_t* epoch_dev, int32_t* index_out,
+                       void* stream) {
+    const int32_t rc = ppo_shuffle_check(e, B, epoch_dev, index_out);
+    if (rc != HG_OK) return rc;
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    int w = 0;
+    for (uint64_t t = (uint64_t)(B - 1); t; t >>= 1) ++w;   // bit_length(B - 1)
+    if (w < 1) w = 1;
+    hipLaunchKernelGGL(ppo_shuffle_kernel, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, index_out, (uint32_t)B,
+                       (uint32_t)seed ^ 0x73687566u, (uint32_t)(seed >> 32) ^ 0x666C655Fu, epoch, epoch_dev, (w + 1) / 2);
+    HIP_TRY(hipGetLastError());
+    return HG_OK;
+}
+
+static int32_t ppo_adam_check(const hg_env* e, const float* theta, const float* grad, const float* stats, const void* state,
+                              const hg_ppo_opt_cfg* cfg) {
+    const int32_t rc = ppo_state_check("hg_ppo_adam", e, state);
+    if (rc != HG_OK) return rc;
+    if (!theta || !grad || !cfg) return fail(HG_E_INVALID, "hg_ppo_adam: theta/grad must be device pointers, cfg a host pointer");
+    if ((((uintptr_t)theta | (uintptr_t)grad | (uintptr_t)stats | (uintptr_t)cfg->lr_dev) & 3) != 0)
+        return fail(HG_E_INVALID, "hg_ppo_adam: theta, grad, stats and lr_dev must be 4-byte aligned");
+    if (!std::isfinite(cfg->lr) || cfg->lr < 0.0) return fail(HG_E_INVALID, "hg_ppo_adam: lr must be finite and >= 0");
+    if (!std::isfinite(cfg->beta1) || cfg->beta1 < 0.0 || cfg->beta1 >= 1.0 || !std::isfinite(cfg->beta2) ||
+        cfg->beta2 < 0.0 || cfg->beta2 >= 1.0)
+        return fail(HG_E_INVALID, "hg_ppo_adam: beta1 and beta2 must be in [0, 1)");
+    if (!std::isfinite(cfg->eps) || cfg->eps < 0.0) return fail(HG_E_INVALID, "hg_ppo_adam: eps must be finite and >= 0");
+    if (std::isnan(cfg->max_grad_norm)) return fail(HG_E_INVALID, "hg_ppo_adam: max_grad_norm is NaN");
+    if (std::isnan(cfg->target_kl)) return fail(HG_E_INVALID, "hg_ppo_adam: target_kl is NaN");
+    return HG_OK;
+}
+
+static hipError_t ppo_adam_launch(float* theta, const float* grad, const float* stats, void* state,
+                                  const hg_ppo_opt_cfg* cfg, hipStream_t stream) {
+    hgk::PpoAdamArgs a;
+    a.theta = theta;
+    a.grad = grad;
+    a.stats = stats;
+    a.state = (uint32_t*)state;
+    a.lr_dev = cfg->lr_dev;
+    a.lr = cfg->lr;
+    a.beta1 = cfg->beta1;
+    a.beta2 = cfg->beta2;
+    a.b1 = (float)cfg->beta1;
+    a.b2 = (float)cfg->beta2;
+    a.omb1 = (float)(1.0 - cfg->beta1);
+    a.omb2 = (float)(1.0 - cfg->beta2);
+    a.eps = (float)cfg->eps;
+    a.max_norm = std::isinf(cfg->max_grad_norm) ? 0.0f : cfg->max_grad_norm;
+    a.target_kl = cfg->target_kl;
+    return hgk::launch_ppo_adam(a, stream);
+}
+
+int32_t hg_ppo_adam(hg_env* e, float* theta, const float* grad, const float* stats, void* state, const hg_ppo_opt_cfg* cfg,
+                    void* stream) {
+    const int32_t rc = ppo_adam_check(e, theta, grad, stats, state, cfg);
+    if (rc != HG_OK) return rc;
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    HIP_TRY(ppo_adam_launch(theta, grad, stats, state, cfg, (hipStream_t)stream));
+    return HG_OK;
+}
+
+int32_t hg_ppo_update(hg_env* e, float* theta, const float* obs_mean, const float* obs_scale, const float* obs,
+                      const float* actions, const float* logp_old, const float* adv, const float* ret, int64_t B, float clip,
+                      float vf_coef, float ent_coef, float* grad, void* workspace, int32_t n_epochs, int32_t n_minibatches,
+                      uint64_t seed, int32_t* index, float* stats_out, void* state, const hg_ppo_opt_cfg* cfg, void* stream) {
+    // every part's checks before anything is enqueued (M = 1 stands for the slices: each has 1 .. B rows)
+    int32_t rc = ppo_shuffle_check(e, B, nullptr, index);
+    if (rc == HG_OK)
+        rc = ppo_grad_check(e, theta, obs_mean, obs_scale, obs, actions, logp_old, adv, ret, B, index, 1, clip, vf_coef,
+                            ent_coef, grad, stats_out, workspace);
+    if (rc == HG_OK) rc = ppo_adam_check(e, theta, grad, stats_out, state, cfg);
+    if (rc != HG_OK) return rc;
+    if (n_epochs < 1) return fail(HG_E_INVALID, "hg_ppo_update: n_epochs must be >= 1");
+    if (n_minibatches < 1 || (int64_t)n_minibatches > B)
+        return fail(HG_E_INVALID, "hg_ppo_update: n_minibatches must be in 1 .. B");
+    if (cfg->target_kl > 0.f && !stats_out)
+        return fail(HG_E_INVALID, "hg_ppo_update: target_kl needs stats_out (the early stop reads each minibatch's row)");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    hipStream_t s = (hipStream_t)stream;
+    int32_t* const tail = (int32_t*)state + hgk::kOptTail;
+    // (a kernel, not a 4-byte memset: replayed memset nodes have left such words stale)
+    hipLaunchKernelGGL(zero_counts_kernel, dim3(1), dim3(64), 0, s, tail + hgk::kOptStop, (int32_t*)nullptr,
+                       (int32_t*)nullptr, (int32_t*)nullptr);
+    HIP_TRY(hipGetLastError());
+    for (int32_t ep = 0; ep < n_epochs; ++ep) {
+        rc = hg_ppo_shuffle(e, B, seed, 0, tail + hgk::kOptSeen, index, stream);
+        if (rc != HG_OK) return rc;
+        for (int32_t j = 0; j < n_minibatches; ++j) {
+            // floor(j B / n): B < 2^31 and n <= B, so the product fits 64 bits
+            const int64_t lo = (int64_t)j * B / n_minibatches, hi = (int64_t)(j + 1) * B / n_minibatches;
+            float* const row = stats_out ? stats_out + 8 * ((int64_t)ep * n_minibatches + j) : nullptr;
+            rc = hg_ppo_grad(e, theta, obs_mean, obs_scale, obs, actions, logp_old, adv, ret, B, index + lo, hi - lo, clip,
+                             vf_coef, ent_coef, grad, row, workspace, stream);
+            if (rc != HG_OK) return rc;
+            HIP_TRY(ppo_adam_launch(theta, grad, row, state, cfg, s));
+        }
+    }
+    return HG_OK;
+}
+
+int32_t hg_set_policy_theta(hg_env* e, const float* theta, const float* obs_mean, const float* obs_scale, void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!theta) return fail(HG_E_INVALID, "hg_set_policy_theta: theta must be a device pointer");
+    if ((((uintptr_t)theta | (uintptr_t)obs_mean | (uintptr_t)obs_scale) & 3) != 0)
+        return fail(HG_E_INVALID, "hg_set_policy_theta: every pointer must be 4-byte aligned");
+    const int32_t rc = hg_set_policy(e, theta + hgk::kPpoW1, theta + hgk::kPpoB1, theta + hgk::kPpoW2, theta + hgk::kPpoB2,
+                                     theta + hgk::kPpoW3, theta + hgk::kPpoB3, theta + hgk::kPpoLogStd, obs_mean, obs_scale,
+                                     stream);
+    if (rc != HG_OK) return rc;
+    return hg_set_value_head(e, theta + hgk::kPpoWv, theta + hgk::kPpoBv, stream);
 }
 
 // The planning calls check their plain arguments before the handle, so that a bad one is refused with

@@ -29,6 +29,7 @@ HG_BRANCH_NOISE_ENV, HG_BRANCH_NOISE_OFF = 0, 1
 BRANCH_NOISE_MODES = {"env": HG_BRANCH_NOISE_ENV, "off": HG_BRANCH_NOISE_OFF}
 HG_ABI_VERSION = 3
 HG_PPO_N_PARAMS = 5641
+HG_PPO_OPT_STATE_BYTES = 45248
 
 AIRFRAME_FIELDS = (
     ["env_R", "env_T0", "env_LAPSE", "env_RO_SEA", "env_GRAV", "env_MAX_GR_ALT", "env_NS_MAX",
@@ -79,6 +80,12 @@ class hg_trim_result(ctypes.Structure):
                 ("failed", ctypes.c_int32)]
 
 
+class hg_ppo_opt_cfg(ctypes.Structure):
+    _fields_ = [("lr", ctypes.c_double), ("lr_dev", ctypes.c_void_p), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double), ("eps", ctypes.c_double), ("max_grad_norm", ctypes.c_float),
+                ("target_kl", ctypes.c_float)]
+
+
 # Every symbol include/heligym_amd.h declares, with its ctypes signature.
 _P = ctypes.c_void_p
 _SIGS = {
@@ -116,6 +123,14 @@ _SIGS = {
     "hg_ppo_grad_workspace_bytes": (ctypes.c_int64, []),
     "hg_ppo_grad": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_float,
                                      ctypes.c_float, ctypes.c_float, _P, _P, _P, _P]),
+    "hg_ppo_opt_state_bytes": (ctypes.c_int64, []),
+    "hg_ppo_opt_init": (ctypes.c_int32, [_P, _P, _P]),
+    "hg_ppo_shuffle": (ctypes.c_int32, [_P, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64, _P, _P, _P]),
+    "hg_ppo_adam": (ctypes.c_int32, [_P, _P, _P, _P, _P, ctypes.POINTER(hg_ppo_opt_cfg), _P]),
+    "hg_ppo_update": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int64, ctypes.c_float, ctypes.c_float,
+                                       ctypes.c_float, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, _P, _P, _P,
+                                       ctypes.POINTER(hg_ppo_opt_cfg), _P]),
+    "hg_set_policy_theta": (ctypes.c_int32, [_P, _P, _P, _P, _P]),
     "hg_rollout_branch": (ctypes.c_int32, [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _P, _P,
                                            _P, _P]),
     "hg_mppi_sample": (ctypes.c_int32, [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float),

@@ -170,6 +170,49 @@ class ActorCriticParams:
         return ppo_views(self.theta)
 
 
+# ---- the optimiser's state on the device (hg_ppo_adam, hg_ppo_update)
+# name -> offset in 4-byte words, include/heligym_amd.h's table: the two moments, then the tail's words
+PPO_OPT_TAIL = 11296
+PPO_OPT_LAYOUT = {
+    "m": 0, "v": 5648,
+    "applied": PPO_OPT_TAIL + 0, "seen": PPO_OPT_TAIL + 1, "stop": PPO_OPT_TAIL + 2,
+    "skipped_nonfinite": PPO_OPT_TAIL + 3, "skipped_stopped": PPO_OPT_TAIL + 4,
+    "last_norm": PPO_OPT_TAIL + 5, "last_clip_coef": PPO_OPT_TAIL + 6,
+}
+PPO_OPT_WORDS = PPO_OPT_TAIL + 16
+PPO_OPT_FLOAT_WORDS = ("last_norm", "last_clip_coef")
+
+
+class PPOOptState:
+    """Adam's state for the flat parameter vector, on `device`, in hg_ppo_adam's layout: `state` is one int32
+    [11312] tensor (45 248 bytes, zeroed: what hg_ppo_opt_init leaves), `m` and `v` float32 [5641] views of it.
+    counters() reads the tail with one copy."""
+
+    def __init__(self, device):
+        import torch
+        self.state = torch.zeros((PPO_OPT_WORDS,), dtype=torch.int32, device=device)
+        self.m = self.state[PPO_OPT_LAYOUT["m"]:PPO_OPT_LAYOUT["m"] + PPO_N_PARAMS].view(torch.float32)
+        self.v = self.state[PPO_OPT_LAYOUT["v"]:PPO_OPT_LAYOUT["v"] + PPO_N_PARAMS].view(torch.float32)
+        self.tail = self.state[PPO_OPT_TAIL:]
+        self.seen = self.tail[1:2]   # the word hg_ppo_update keys its permutations on
+
+    def zero_(self):
+        self.state.zero_()
+        return self
+
+    def counters(self):
+        """{applied, seen, stop, skipped_nonfinite, skipped_stopped: int; last_norm, last_clip_coef: float}
+        (one device-to-host copy, which synchronises)."""
+        import numpy as np
+        t = self.tail.cpu().numpy()
+        out = {}
+        for k, off in PPO_OPT_LAYOUT.items():
+            if off >= PPO_OPT_TAIL:
+                w = t[off - PPO_OPT_TAIL:off - PPO_OPT_TAIL + 1]
+                out[k] = float(w.view(np.float32)[0]) if k in PPO_OPT_FLOAT_WORDS else int(w[0])
+        return out
+
+
 def ppo_loss(theta_or_params, obs, actions, logp_old, adv, ret, clip, vf_coef, ent_coef, obs_mean=None,
              obs_scale=None):
     """The clipped PPO loss hg_ppo_grad differentiates (include/heligym_amd.h), in plain torch and in the

@@ -757,6 +757,153 @@ class HeliVecEnv(*_VEC_BASES):
                                          float(ent_coef), _ptr(grad), _ptr(st), _ptr(ws), self._stream()))
         return grad, st
 
+    # ------------------------------------------------------------------ the PPO update on the device
+    def _opt_tensor(self, x, shape, name, dtype=None, who="ppo_update"):
+        t = self.torch
+        dtype = t.float32 if dtype is None else dtype
+        if (not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device or not x.is_contiguous()
+                or tuple(x.shape) != tuple(shape)):
+            got = f"{tuple(x.shape)} {x.dtype} on {x.device}" if isinstance(x, t.Tensor) else type(x).__name__
+            raise ValueError(f"{who}: {name} must be a contiguous {dtype} {tuple(shape)} tensor on {self.device}, got {got}")
+        return x
+
+    def _opt_cfg(self, who, lr, betas, eps, max_grad_norm, target_kl, lr_dev):
+        """The hg_ppo_opt_cfg of the keyword arguments (ValueError for what hg_ppo_adam would refuse)."""
+        import math
+        try:
+            lr, eps, (b1, b2) = float(lr), float(eps), (float(b) for b in betas)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: lr and eps must be numbers and betas a pair of numbers") from None
+        if not math.isfinite(lr) or lr < 0:
+            raise ValueError(f"{who}: lr must be finite and >= 0, got {lr}")
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"{who}: betas must be in [0, 1), got {(b1, b2)}")
+        if not math.isfinite(eps) or eps < 0:
+            raise ValueError(f"{who}: eps must be finite and >= 0, got {eps}")
+        mg = 0.0 if max_grad_norm is None else float(max_grad_norm)
+        kl = 0.0 if target_kl is None else float(target_kl)
+        if math.isnan(mg) or math.isnan(kl):
+            raise ValueError(f"{who}: max_grad_norm and target_kl must not be NaN")
+        p = None
+        if lr_dev is not None:
+            t = self.torch
+            if (not isinstance(lr_dev, t.Tensor) or lr_dev.dtype != t.float32 or lr_dev.device != self.device
+                    or lr_dev.numel() != 1):
+                raise ValueError(f"{who}: lr_dev must be a float32 tensor of one element on {self.device}")
+            p = lr_dev.data_ptr()
+        return _abi.hg_ppo_opt_cfg(lr, p, b1, b2, eps, mg, kl)
+
+    def _opt_state(self, state, who):
+        from . import policy
+        s = getattr(state, "state", None)
+        return self._opt_tensor(s, (policy.PPO_OPT_WORDS,), "state.state (a PPOOptState)", self.torch.int32, who)
+
+    def ppo_shuffle(self, B, seed, epoch=0, epoch_dev=None, out=None):
+        """A stateless random permutation of 0..B-1 as an int32 [B] device tensor (hg_ppo_shuffle: a keyed
+        Feistel network with cycle walking, no sort).  The key is (seed, epoch + *epoch_dev): epoch_dev, an
+        int32 device tensor of one element (a PPOOptState's `seen`), is read when the kernel runs."""
+        t = self.torch
+        B = int(B)
+        if B < 1 or B > 2 ** 31 - 256:
+            raise ValueError(f"ppo_shuffle: B must be in 1 .. 2^31 - 256, got {B}")
+        if epoch_dev is not None and (not isinstance(epoch_dev, t.Tensor) or epoch_dev.dtype != t.int32
+                                      or epoch_dev.device != self.device or epoch_dev.numel() != 1):
+            raise ValueError(f"ppo_shuffle: epoch_dev must be an int32 tensor of one element on {self.device}")
+        if out is None:
+            out = t.empty((B,), dtype=t.int32, device=self.device)
+        out = self._opt_tensor(out, (B,), "out", t.int32, "ppo_shuffle")
+        self._keep_shuffle = epoch_dev
+        self._check(self.lib.hg_ppo_shuffle(self._h, B, int(seed) & (2 ** 64 - 1), int(epoch), _ptr(epoch_dev), _ptr(out),
+                                            self._stream()))
+        return out
+
+    def ppo_adam(self, params, state, stats=None, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None,
+                 target_kl=None, lr_dev=None):
+        """One optimiser step on the device (hg_ppo_adam): params.theta is updated in place from params.grad
+        (not modified) and `state` (a PPOOptState): the approximate-KL early stop on `stats` [8] (ppo_grad's,
+        of the same minibatch; with target_kl), the non-finite guard, global gradient-norm clipping
+        (max_grad_norm, torch's clip_grad_norm_) and Adam with fp64 bias corrections.  lr_dev: a float32
+        device tensor of one element read when the kernel runs, in place of lr.  Asynchronous, allocates
+        nothing, capturable."""
+        theta = self._opt_tensor(getattr(params, "theta", None), (_abi.HG_PPO_N_PARAMS,), "params.theta", who="ppo_adam")
+        grad = self._opt_tensor(getattr(params, "grad", None), (_abi.HG_PPO_N_PARAMS,), "params.grad", who="ppo_adam")
+        st = None if stats is None else self._opt_tensor(stats, (8,), "stats", who="ppo_adam")
+        s = self._opt_state(state, "ppo_adam")
+        cfg = self._opt_cfg("ppo_adam", lr, betas, eps, max_grad_norm, target_kl, lr_dev)
+        self._keep_adam = (theta, grad, st, s, lr_dev)
+        self._check(self.lib.hg_ppo_adam(self._h, _ptr(theta), _ptr(grad), _ptr(st), _ptr(s), ctypes.byref(cfg),
+                                         self._stream()))
+        return theta
+
+    def set_policy_theta(self, params, obs_mean=None, obs_scale=None):
+        """set_policy + set_value_head from the flat vector params.theta (hg_set_policy_theta), bitwise those
+        two calls on the actor, log_std and the critic; on the current stream, capturable."""
+        theta = self._opt_tensor(getattr(params, "theta", None), (_abi.HG_PPO_N_PARAMS,), "params.theta",
+                                 who="set_policy_theta")
+        mean = None if obs_mean is None else self._opt_tensor(obs_mean, (_abi.HG_N_OBS,), "obs_mean", who="set_policy_theta")
+        scale = None if obs_scale is None else self._opt_tensor(obs_scale, (_abi.HG_N_OBS,), "obs_scale",
+                                                                who="set_policy_theta")
+        self._keep_policy_theta = (theta, mean, scale)
+        self._check(self.lib.hg_set_policy_theta(self._h, _ptr(theta), _ptr(mean), _ptr(scale), self._stream()))
+
+    def ppo_update(self, params, state, obs, actions, logp_old, adv, ret, epochs=4, minibatches=4, seed=0, clip=0.2,
+                   vf_coef=1.0, ent_coef=0.0, obs_mean=None, obs_scale=None, lr=3e-4, betas=(0.9, 0.999), eps=1e-8,
+                   max_grad_norm=None, target_kl=None, lr_dev=None, stats=None, index=None, publish=False):
+        """The whole update phase in one call (hg_ppo_update): `epochs` times a fresh permutation of the B
+        stored rows (keyed by `seed` and the state's `seen` counter), cut into `minibatches` slices, and for
+        each slice ppo_grad then ppo_adam, all enqueued on the current stream with no host decision in
+        between.  The rows are ppo_grad's (leading dimensions are merged), the optimiser's arguments
+        ppo_adam's.  Returns the statistics rows [epochs * minibatches, 8] (`stats`: such a tensor to reuse);
+        `index`: an int32 [B] scratch tensor to reuse (it holds the last epoch's permutation afterwards).
+        publish=True ends with set_policy_theta(params, obs_mean, obs_scale).  Bitwise the same calls made
+        one by one; allocates nothing after the first call with these shapes; capturable."""
+        t = self.torch
+        who = "ppo_update"
+        theta = self._opt_tensor(getattr(params, "theta", None), (_abi.HG_PPO_N_PARAMS,), "params.theta")
+        grad = self._opt_tensor(getattr(params, "grad", None), (_abi.HG_PPO_N_PARAMS,), "params.grad")
+        s = self._opt_state(state, who)
+        if not isinstance(obs, t.Tensor) or obs.ndim < 2 or obs.shape[-1] != _abi.HG_N_OBS:
+            raise ValueError("ppo_update: obs must be a [..., 17] tensor")
+        B = int(obs.numel() // _abi.HG_N_OBS)
+        if B < 1 or B > 2 ** 31 - 256:
+            raise ValueError(f"ppo_update: obs must have 1 .. 2^31 - 256 rows, got {B}")
+        lead = tuple(obs.shape[:-1])
+        o = self._opt_tensor(obs, lead + (_abi.HG_N_OBS,), "obs")
+        a = self._opt_tensor(actions, lead + (_abi.HG_N_ACT,), "actions")
+        lp = self._opt_tensor(logp_old, lead, "logp_old")
+        ad = self._opt_tensor(adv, lead, "adv")
+        rt = self._opt_tensor(ret, lead, "ret")
+        epochs, minibatches = int(epochs), int(minibatches)
+        if epochs < 1:
+            raise ValueError(f"ppo_update: epochs must be >= 1, got {epochs}")
+        if minibatches < 1 or minibatches > B:
+            raise ValueError(f"ppo_update: minibatches must be in 1 .. {B} (the rows), got {minibatches}")
+        mean = None if obs_mean is None else self._opt_tensor(obs_mean, (_abi.HG_N_OBS,), "obs_mean")
+        scale = None if obs_scale is None else self._opt_tensor(obs_scale, (_abi.HG_N_OBS,), "obs_scale")
+        cfg = self._opt_cfg(who, lr, betas, eps, max_grad_norm, target_kl, lr_dev)
+        if stats is None:
+            stats = getattr(self, "_ppo_update_stats", None)
+            if stats is None or tuple(stats.shape) != (epochs * minibatches, 8):
+                stats = self._ppo_update_stats = t.empty((epochs * minibatches, 8), dtype=t.float32, device=self.device)
+        st = self._opt_tensor(stats, (epochs * minibatches, 8), "stats")
+        if index is None:
+            index = getattr(self, "_ppo_update_index", None)
+            if index is None or tuple(index.shape) != (B,):
+                index = self._ppo_update_index = t.empty((B,), dtype=t.int32, device=self.device)
+        ix = self._opt_tensor(index, (B,), "index", t.int32)
+        ws = getattr(self, "_ppo_workspace", None)
+        if ws is None:
+            ws = self._ppo_workspace = t.empty((int(self.lib.hg_ppo_grad_workspace_bytes()),), dtype=t.uint8,
+                                               device=self.device)
+        self._keep_ppo_update = (theta, grad, s, o, a, lp, ad, rt, mean, scale, st, ix, lr_dev)
+        self._check(self.lib.hg_ppo_update(self._h, _ptr(theta), _ptr(mean), _ptr(scale), _ptr(o), _ptr(a), _ptr(lp),
+                                           _ptr(ad), _ptr(rt), B, float(clip), float(vf_coef), float(ent_coef), _ptr(grad),
+                                           _ptr(ws), epochs, minibatches, int(seed) & (2 ** 64 - 1), _ptr(ix), _ptr(st),
+                                           _ptr(s), ctypes.byref(cfg), self._stream()))
+        if publish:
+            self.set_policy_theta(params, mean, scale)
+        return st
+
     # ------------------------------------------------------------------ branched planning rollouts
     def _plan_tensor(self, x, shape, name, dtype=None):
         """`x` as the library reads it: a contiguous tensor of `shape` and `dtype` on the env's device

@@ -410,6 +410,109 @@ int32_t hg_ppo_grad(hg_env* env, const float* theta_dev,           /* [5641] the
                     float* stats_dev,     /* [8] out or NULL */
                     void* workspace_dev, void* stream);
 
+/* ---- The update phase on the device: minibatch shuffle, gradient clipping, Adam, and all of it in one call.
+ *
+ * Every call below is asynchronous on `stream`, allocates nothing, makes no host decision that depends on
+ * device data and can be captured into a graph; `env` is used for its device and the error convention
+ * only and is not modified (hg_set_policy_theta excepted: it is hg_set_policy + hg_set_value_head).
+ *
+ * Optimiser state: hg_ppo_opt_state_bytes() = 45248 bytes of device memory, 16-byte aligned, owned by the
+ * caller.  In 4-byte words (offset: content):
+ *       0: m [5641] fp32, Adam's first moment, in theta's layout
+ *    5648: v [5641] fp32, the second moment
+ *   11296: a tail of 16 words:
+ *          +0 applied            i32  Adam steps taken: the t of the bias corrections
+ *          +1 seen               i32  hg_ppo_adam calls, applied or not
+ *          +2 stop               i32  set by the approximate-KL early stop, cleared by hg_ppo_update's start
+ *          +3 skipped_nonfinite  i32  calls dropped because the gradient norm was not finite
+ *          +4 skipped_stopped    i32  calls dropped because `stop` was set (the one that set it included)
+ *          +5 last_norm          fp32 the last computed gradient norm, before clipping
+ *          +6 last_clip_coef     fp32 the last applied clip coefficient
+ *          +7 .. +15             reserved, zero
+ *   (words 5641 .. 5647 and 11289 .. 11295 are padding, zero.)
+ * hg_ppo_opt_init zeroes the state (one kernel). */
+int64_t hg_ppo_opt_state_bytes(void);           /* fixed; a multiple of 16; host only */
+int32_t hg_ppo_opt_init(hg_env* env, void* state_dev, void* stream);
+
+/* A stateless random permutation of 0 .. B-1 into index_out_dev [B] i32: no sort, no scratch memory.
+ *   e = epoch + (epoch_dev ? *epoch_dev : 0), a 64-bit sum; epoch_dev is read when the kernel runs, so a
+ *       replayed graph whose epoch_dev points at a counter draws a new permutation every replay.
+ *   w = max(1, bit_length(B - 1)),  half = ceil(w / 2),  mask = 2^half - 1.
+ *   Element i starts at x = i.  One pass: L = x >> half, R = x & mask; four Feistel rounds j = 0 .. 3,
+ *       (L, R) <- (R, L ^ (F(R, j) & mask));  x = (L << half) | R.
+ *   Passes repeat while x >= B (cycle walking); index[i] is the first x < B.  The passes permute
+ *   [0, 4^half), a domain under 4 B, and the orbit of i returns to i < B: the walk always ends, after
+ *   under 4 passes in the mean.
+ *   F(R, j) = word 0 of Philox4x32-10 on the counter (R, j, e_lo, e_hi) with the key
+ *   (seed_lo ^ 0x73687566, seed_hi ^ 0x666C655F).
+ * HG_E_INVALID, output untouched: NULL env; NULL index_out_dev; a misaligned (4 bytes) pointer; B < 1;
+ * B > 2^31 - 256. */
+int32_t hg_ppo_shuffle(hg_env* env, int64_t B, uint64_t seed, int64_t epoch, const int32_t* epoch_dev,
+                       int32_t* index_out_dev, void* stream);
+
+/* The optimiser's settings: a host struct, read when the call is made. */
+typedef struct hg_ppo_opt_cfg {
+    double lr;             /* learning rate */
+    const float* lr_dev;   /* device pointer or NULL; if set the kernel uses *lr_dev, read when it runs, in
+                              place of lr: a schedule is one 4-byte copy between replays of a captured graph */
+    double beta1, beta2;   /* Adam's betas, in [0, 1) */
+    double eps;            /* Adam's epsilon */
+    float max_grad_norm;   /* global gradient-norm clip; <= 0 or +inf: off */
+    float target_kl;       /* approximate-KL early stop; <= 0: off */
+} hg_ppo_opt_cfg;
+
+/* One optimiser step: theta_dev [5641] updated in place from grad_dev [5641] (not modified); stats_dev
+ * [8], hg_ppo_grad's statistics of the minibatch grad_dev came from, or NULL.  With the tail's words of
+ * state_dev as named above, in this order:
+ *   1. seen += 1.
+ *   2. If stop is set: skipped_stopped += 1, done.
+ *   3. If target_kl > 0 and stats_dev is given and stats[2] > 1.5 target_kl (fp32): set stop,
+ *      skipped_stopped += 1, done.  (The usual rule: stats[2] was measured at the weights the previous
+ *      steps left, so this minibatch and every later one are dropped until stop is cleared.)
+ *   4. nrm = sqrt(sum g^2) in fp32, in a fixed order that depends on compile-time constants only
+ *      (csrc/ppo_opt.hip states it); last_norm = nrm.
+ *   5. If nrm is not finite: skipped_nonfinite += 1, done; theta, m, v and applied stay bitwise as they are.
+ *   6. c = max_grad_norm on ? min(1, max_grad_norm / (nrm + 1e-6)) : 1  (torch's clip_grad_norm_);
+ *      last_clip_coef = c.
+ *   7. g' = c g.
+ *   8. applied += 1;  t = applied.
+ *   9. m = fma(beta1, m, (1 - beta1) g');   v = fma(beta2, v, ((1 - beta2) g') g').
+ *  10. theta = fma(-(lr / (1 - beta1^t)), m / fma(sqrt(v), 1 / sqrt(1 - beta2^t), eps), theta).
+ * Precision: lr / (1 - beta1^t) and 1 / sqrt(1 - beta2^t) are formed in fp64 on the device from the double
+ * betas, t and lr (or (double)*lr_dev) and rounded to fp32 once; beta, 1 - beta and eps are rounded to
+ * fp32 once from double; everything per element is fp32.
+ * Deterministic: one block, no atomics; two calls on equal inputs give equal bits.
+ * HG_E_INVALID, nothing touched: NULL env; NULL theta_dev, grad_dev, state_dev or cfg; a misaligned pointer
+ * (4 bytes; state_dev 16); lr or eps non-finite or negative; a beta outside [0, 1) or non-finite; NaN
+ * max_grad_norm or target_kl. */
+int32_t hg_ppo_adam(hg_env* env, float* theta_dev, const float* grad_dev, const float* stats_dev, void* state_dev,
+                    const hg_ppo_opt_cfg* cfg, void* stream);
+
+/* The whole update phase, enqueued by one call.  The arguments up to workspace_dev are hg_ppo_grad's
+ * (theta_dev is also written); index_dev [B] i32 is scratch for the permutations; stats_out_dev
+ * [n_epochs * n_minibatches, 8] receives each minibatch's statistics row, or NULL -- but target_kl > 0
+ * REQUIRES stats_out_dev (the early stop reads the row): HG_E_INVALID without it.
+ *   stop = 0 (one single-thread kernel);
+ *   for each epoch:  hg_ppo_shuffle(B, seed, epoch = 0, epoch_dev = the state's `seen` word) -> index_dev;
+ *     for minibatch j = 0 .. n_minibatches-1, rows [floor(j B / n), floor((j + 1) B / n)) of index_dev:
+ *       hg_ppo_grad over that slice (its two launches) -> grad_dev and the minibatch's stats row,
+ *       hg_ppo_adam(theta_dev, grad_dev, that row, state_dev, cfg).
+ * `seen` advances with every optimiser call, so every epoch of every call, and every replay of a captured
+ * call, draws another permutation.  The results are bitwise those of the same calls made one by one.
+ * HG_E_INVALID before anything is enqueued: what hg_ppo_shuffle, hg_ppo_grad and hg_ppo_adam refuse;
+ * n_epochs < 1; n_minibatches outside 1 .. B. */
+int32_t hg_ppo_update(hg_env* env, float* theta_dev, const float* obs_mean_dev, const float* obs_scale_dev,
+                      const float* obs_dev, const float* actions_dev, const float* logp_old_dev, const float* adv_dev,
+                      const float* ret_dev, int64_t B, float clip, float vf_coef, float ent_coef, float* grad_dev,
+                      void* workspace_dev, int32_t n_epochs, int32_t n_minibatches, uint64_t seed, int32_t* index_dev,
+                      float* stats_out_dev, void* state_dev, const hg_ppo_opt_cfg* cfg, void* stream);
+
+/* Publish the learner's weights to the env: hg_set_policy + hg_set_value_head on the tensors of a flat
+ * theta_dev [5641] (log_std included: a stochastic policy), bitwise those two calls.  obs_mean_dev /
+ * obs_scale_dev [17] or NULL. */
+int32_t hg_set_policy_theta(hg_env* env, const float* theta_dev, const float* obs_mean_dev, const float* obs_scale_dev,
+                            void* stream);
+
 /* ---- Branched planning rollouts: many candidate action sequences per env, scored without touching it.
  *
  * What a receding-horizon sampling planner (MPPI, CEM, random shooting) needs from the rollout: `branches`
