@@ -8,7 +8,8 @@
   3. the value head against a float64 forward pass, measured against a float32 NumPy one;
   4. the log-probabilities: against the host restatement of the noise, and as a learner recomputes them
      from the stored observations and actions;
-  5. hg_gae against a float64 reverse loop, measured against the float32 loop;
+  5. hg_gae against a float64 reverse loop, measured against the float32 loop; its two loops' hand-off
+     (K % 4 != 0, K > 4) also bitwise against the four-at-a-time loop alone; more than one block;
   6. set_policy / set_value_head commute, and the whole collection step in one graph;
   7. argument errors leave the env untouched.
 Run with -m gpu."""
@@ -324,6 +325,79 @@ def test_gae_against_float64(torch, gae_inputs, n, k, gamma, lam):
         mag = np.abs(r).astype(np.float64) + gamma * np.abs(nv) + np.abs(v)
         assert np.all(np.abs(adv - delta) <= 2 * _ulp32(mag))
     env.close()
+
+
+@pytest.fixture(scope="module")
+def gae_inputs_wide():
+    """gae_inputs' draws at K = 13, N = 1 000: more than one 256-thread block, the last one ragged."""
+    rng = np.random.RandomState(18)
+    k, n = 13, 1000
+    r = rng.standard_normal((k, n)).astype(np.float32)
+    v = (3.0 * rng.standard_normal((k, n))).astype(np.float32)
+    nv = (3.0 * rng.standard_normal((k, n))).astype(np.float32)
+    term = rng.random_sample((k, n)) < 0.10
+    trunc = rng.random_sample((k, n)) < 0.10
+    both = rng.random_sample((k, n)) < 0.02
+    term, trunc = term | both, trunc | both
+    nv[term] = 0.0
+    assert (term & trunc).sum() >= 3 and (term[0] | trunc[0]).any()
+    return r, v, nv, term, trunc
+
+
+def _gae_on_device(torch, env, r, v, nv, term, trunc, gamma=0.99, lam=0.95):
+    dev = lambda x: torch.as_tensor(np.ascontiguousarray(x), device="cuda:0")   # noqa: E731
+    adv, ret = env.gae(dev(r), dev(v), dev(nv), dev(term), dev(trunc.astype(np.uint8)), gamma=gamma, lam=lam)
+    return adv.cpu().numpy(), ret.cpu().numpy()
+
+
+# The kernel takes the steps four at a time from the last one back while k >= 3, then one at a time, carrying A:
+#   K   four at a time    one at a time
+#   2   -                 1, 0
+#   3   -                 2, 1, 0
+#   4   3..0              -
+#   5   4..1              0            (K % 4 = 1: A handed from the first loop to the second)
+#   6   5..2              1, 0         (K % 4 = 2)
+#   7   6..3              2, 1, 0      (K % 4 = 3)
+#  13   12..9, 8..5, 4..1 0            (A through three rounds of the first loop, then handed on)
+# n = 257: two blocks, the second with one lane; n = 1 000: four blocks, the last with 232 lanes.
+@pytest.mark.parametrize("n", [257, 1000])
+@pytest.mark.parametrize("k", [2, 3, 4, 5, 6, 7, 13])
+def test_gae_loop_hand_off_and_blocks_against_float64(torch, gae_inputs_wide, n, k):
+    """test_gae_against_float64's check where both of the kernel's loops run and past one block."""
+    gamma, lam = 0.99, 0.95
+    r, v, nv, term, trunc = (x[:k, :n] for x in gae_inputs_wide)
+    env = _env(torch, n)
+    adv, ret = _gae_on_device(torch, env, r, v, nv, term, trunc, gamma, lam)
+    env.close()
+    done = term | trunc
+    ref = _gae_loop(r, v, nv, done, gamma, lam, np.float64)
+    err32 = np.abs(_gae_loop(r, v, nv, done, gamma, lam, np.float32).astype(np.float64) - ref).max()
+    err = np.abs(adv.astype(np.float64) - ref).max()
+    floor = 4 * float(np.spacing(np.float32(np.abs(ref).max())))
+    print(f"\n[gae N={n} K={k} gamma={gamma} lam={lam}] kernel max|d| {err:.3e}, float32 loop {err32:.3e} "
+          f"(floor {floor:.3e}, max|A| {np.abs(ref).max():.2f})")
+    assert err <= max(4 * err32, floor)
+    np.testing.assert_array_equal(ret.view(np.int32), (adv + v).view(np.int32))
+
+
+@pytest.mark.parametrize("k", [5, 6, 7])
+def test_gae_hand_off_is_bitwise_the_unrolled_loop(torch, gae_inputs_wide, k):
+    """K steps that end in a termination, against the same rows as the first K of 8 steps: the 8-step call takes
+    the rows 7..4 and 3..0 four at a time, the K-step call hands A from the four-at-a-time loop to the
+    one-at-a-time loop (K % 4 = 1, 2, 3).  Every env is cut at row K - 1, so nothing of the later rows enters:
+    rows 0 .. K-1 must be the same bits."""
+    n = 1000
+    r, v, nv, term, trunc = (x[:8, :n].copy() for x in gae_inputs_wide)
+    term[k - 1, :], nv[k - 1, :] = True, 0.0
+    env = _env(torch, n)
+    short = _gae_on_device(torch, env, *(x[:k] for x in (r, v, nv, term, trunc)))
+    long = _gae_on_device(torch, env, r, v, nv, term, trunc)
+    env.close()
+    assert np.isfinite(long[0]).all() and np.abs(long[0][k:]).max() > 0   # (the later rows are live)
+    for a, b, what in zip(short, long, ("advantages", "returns")):
+        np.testing.assert_array_equal(a.view(np.int32), b[:k].view(np.int32), err_msg=what)
+    for adv, ret in (short, long):
+        np.testing.assert_array_equal(ret.view(np.int32), (adv + v[:len(adv)]).view(np.int32))
 
 
 def test_gae_flags_cut_the_chain(torch, gae_inputs):

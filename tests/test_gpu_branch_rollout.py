@@ -11,7 +11,8 @@ rewards, flags and info, cut at the first end.
   2. gamma = 0.99 against a float64 recurrence over B's fp32 rewards;
   3. the env is untouched;  4. envs waiting for their next-step reset, and a RETRIM handle;
   5. the launches past one and past two waves per SIMD (the bulk variant);
-  6. mppi_sample;  7. / 8. mppi_update;  9. graph capture;  10. errors.
+  6. mppi_sample;  7. / 8. mppi_update, also at horizons past one pass of its wave (4 * horizon > 64, > 256)
+     and at branch counts past the weights it keeps in LDS (> 1024);  9. graph capture;  10. errors.
 
 A failure termination cannot be forced within 12 steps (0.12 s) by any action in [-1, 1]: from the trim at
 100 ft the descent rate, the attitude limits and the ground are all out of reach in that time.  It is
@@ -413,6 +414,96 @@ def test_mppi_update_general_case(torch, branches):
     again = env.mppi_update(torch.as_tensor(acts, device=DEV), torch.as_tensor(G, device=DEV), lam).cpu().numpy()
     env.close()
     np.testing.assert_array_equal(again[:, 5].view(np.int32), got32[:, 5].view(np.int32))
+
+
+def _update_inputs(seed, n, branches, h, lam):
+    """Returns and candidates drawn as test_mppi_update_general_case draws them, every return finite."""
+    rng = np.random.RandomState(seed)
+    G = (3.0 - 10.0 * rng.rand(n, branches)).astype(np.float32)
+    acts = rng.uniform(-1, 1, size=(h, n * branches, 4)).astype(np.float32)
+    assert ((G.max(1, keepdims=True) - G) / lam).max() <= 20   # no weight underflows
+    return G, acts
+
+
+def _update_values(torch, env, what, acts, G, lam):
+    """The kernel's result, checked against float64 with test_mppi_update_general_case's yardstick over the envs
+    that have a finite return."""
+    fin = np.isfinite(G)
+    gaps = np.where(fin, np.where(fin, G, -np.inf).max(1, keepdims=True) - G, 0) / lam
+    assert gaps.max() <= 20
+    got32 = env.mppi_update(torch.as_tensor(acts, device=DEV), torch.as_tensor(G, device=DEV), lam).cpu().numpy()
+    ref = _update_ref(acts, G, lam, np.float64)
+    r32 = _update_ref(acts, G, lam, np.float32)
+    some = fin.any(1)
+    err = np.abs(got32.astype(np.float64) - ref)[:, some].max()
+    err32 = np.abs(r32.astype(np.float64) - ref)[:, some].max()
+    print(f"\n[mppi_update {what}] kernel max|d| {err:.3e}, float32 NumPy max|d| {err32:.3e}, ratio {err / err32:.2f} (bound 4)")
+    assert np.isfinite(got32).all() and err32 > 0
+    assert err <= 4 * err32
+    return got32
+
+
+# The update kernel's lane owns the elements j0, j0 + 64, j0 + 128, j0 + 192 (q = 0 .. 3) of the env's
+# nel = 4 * horizon and starts again at j0 + 256; a chain past the end reads element j0 once more and is not stored.
+#   horizon  nel
+#     16      64   one pass, q = 0 alone, every lane live
+#     17      68   q = 1 has 4 live lanes, 60 padded ones beside them
+#     30     120   examples/mppi_hover.py's default: q = 1 with 56 live lanes
+#     64     256   all four chains full, one trip
+#     65     260   a second trip of 4 lanes (q = 0 only)
+#    100     400   a second trip with q = 0, 1 full and q = 2 with 16 lanes
+@pytest.mark.parametrize("h", [16, 17, 30, 64, 65, 100])
+def test_mppi_update_past_one_pass_of_the_wave(torch, h):
+    """Values; and every row t of the result is bitwise the horizon-1 call (nel = 4: lanes 0-3, q = 0, one trip)
+    on that step's candidates, whatever lane, chain and trip the longer call gave it."""
+    n, branches, lam = 3, 7, 0.5   # (one wave per env: the kernel does not depend on N)
+    G, acts = _update_inputs(100 + h, n, branches, h, lam)
+    env = _env(torch, n)
+    got = _update_values(torch, env, f"H={h} B={branches}", acts, G, lam)
+    a, g = torch.as_tensor(acts, device=DEV), torch.as_tensor(G, device=DEV)
+    rows = torch.cat([env.mppi_update(a[t:t + 1], g, lam) for t in range(h)])
+    env.close()
+    np.testing.assert_array_equal(rows.cpu().numpy().view(np.int32), got.view(np.int32))
+
+
+# Past HG_MPPI_LDS_BRANCHES = 1024 the weights are recomputed per element in place of read from LDS:
+# 1024 is the last size that keeps them, 1025 the first that does not, 1100 = 17 * 64 + 12 a ragged one.
+@pytest.mark.parametrize("branches", [1024, 1025, 1100])
+def test_mppi_update_past_the_lds_weights(torch, branches):
+    n, h, lam = 3, 5, 0.5
+    G, acts = _update_inputs(branches, n, branches, h, lam)
+    a4 = acts.reshape(h, n, branches, 4)
+    if branches == 1025:
+        G[1, :] = np.nan       # no finite return: branch 0's rows
+        G[2, 513] = np.nan     # a NaN return weighs nothing
+    env = _env(torch, n)
+    got = _update_values(torch, env, f"H={h} B={branches}", acts, G, lam)
+    if branches == 1025:
+        np.testing.assert_array_equal(got[:, 1].view(np.int32), a4[:, 1, 0].view(np.int32))
+        a4[:, 2, 513] = 1e30   # the NaN branch's actions do not enter: replacing them changes nothing
+        again = env.mppi_update(torch.as_tensor(acts, device=DEV), torch.as_tensor(G, device=DEV), lam).cpu().numpy()
+        np.testing.assert_array_equal(again.view(np.int32), got.view(np.int32))
+    env.close()
+
+
+def test_mppi_update_recomputed_weights_are_bitwise_the_lds_ones(torch):
+    """1024 branches (weights from LDS) against the same with a 1025th branch whose return is NaN (weights
+    recomputed): each element's chain runs over b ascending, the last branch weighs 0 and fma(0, a, num) = num
+    for a finite a and a non-zero num, so the bits are the same."""
+    n, h, lam, branches = 3, 5, 0.5, 1024
+    G, acts = _update_inputs(branches, n, branches, h, lam)
+    a4 = acts.reshape(h, n, branches, 4)
+    # no partial sum of a chain is zero (float64, b ascending)
+    w = np.exp2((G.astype(np.float64) - G.max(1, keepdims=True)) * (1.4426950408889634 / lam))
+    assert (np.cumsum(w[None, :, :, None] * a4, axis=2) != 0).all()
+    extra = np.random.RandomState(7).uniform(-1, 1, size=(h, n, 1, 4)).astype(np.float32)
+    acts1 = np.ascontiguousarray(np.concatenate([a4, extra], axis=2).reshape(h, n * (branches + 1), 4))
+    G1 = np.concatenate([G, np.full((n, 1), np.nan, np.float32)], axis=1)
+    env = _env(torch, n)
+    lds = env.mppi_update(torch.as_tensor(acts, device=DEV), torch.as_tensor(G, device=DEV), lam)
+    rec = env.mppi_update(torch.as_tensor(acts1, device=DEV), torch.as_tensor(G1, device=DEV), lam)
+    _assert_same(torch, rec, lds, "1025 branches, the last one NaN, against 1024")
+    env.close()
 
 
 def test_graph_capture(torch):

@@ -3,6 +3,8 @@
   1. values: the gradient and the statistics against heligym_amd.policy.ppo_loss in float64 on the CPU,
      measured against float32 CPU torch autograd of the same expression;
   2. an index is bitwise the materialised rows; out-of-range entries are skipped and counted;
+     and the same past the kernels' loop thresholds (a wave's second and third tile, the reduction's
+     sixteen-deep batches, the block cap), with an index of up to 131 139 draws from the stored rows;
   3. clip semantics: a batch clipped out entirely leaves only the entropy term's gradient;
   4. determinism, and a captured call replayed on changed weights;
   5. consistency with the rollout that produced the data;
@@ -84,8 +86,8 @@ def loss_on(torch, d, theta, rows, dtype, clip=CLIP, vf=VF, ent=ENT, logp_old=No
     c = lambda t: t[rows].to(dtype)   # noqa: E731
     th = theta.detach().cpu().to(dtype).clone().requires_grad_(True)
     lp = d.logp_old if logp_old is None else logp_old
-    L, stats = ppo_loss(th, c(d.obs), c(d.actions), c(lp), c(d.adv), c(d.ret), clip, vf, ent, d.mean.to(dtype),
-                        d.scale.to(dtype))
+    L, stats = ppo_loss(th, c(d.obs), c(d.actions), c(lp), c(d.adv), c(d.ret), clip, vf, ent,
+                        None if d.mean is None else d.mean.to(dtype), None if d.scale is None else d.scale.to(dtype))
     if divisor is not None:
         k = len(rows) / divisor
         H = ppo_views(th)["log_std"].sum() + 2.0 * (1.0 + LOG_2PI)
@@ -101,7 +103,7 @@ def ratios(torch, d, theta, logp_old=None):
     """float64 probability ratios of every stored row under `theta`."""
     from heligym_amd.policy import LOG_2PI, ppo_views
     p = ppo_views(theta.detach().cpu().double())
-    x = (d.obs.double() - d.mean.double()) * d.scale.double()
+    x = d.obs.double() if d.mean is None else (d.obs.double() - d.mean.double()) * d.scale.double()
     h2 = torch.tanh(torch.tanh(x @ p["W1"].T + p["b1"]) @ p["W2"].T + p["b2"])
     z = (d.actions.double() - (h2 @ p["W3"].T + p["b3"])) * torch.exp(-p["log_std"])
     logp = -0.5 * (z * z).sum(-1) - p["log_std"].sum() - 2 * LOG_2PI
@@ -192,6 +194,111 @@ def test_values_against_float64(torch, data, env, m):
     assert float(ref[0].abs().max()) > 1e-3   # a non-trivial gradient
     check_values(torch, f"M={m}", got, st, ref)
     assert float(st[7]) == 0.0
+
+
+def test_values_without_normalisation(torch, data, env):
+    """obs_mean = obs_scale = NULL: the kernel reads the observations as they are.  The rows are the module's,
+    normalised beforehand in float32 on the CPU; the reference is ppo_loss of those float32 inputs without
+    a normalisation."""
+    m = 65   # two tiles, the second one lane
+    x = (data.obs - data.mean) * data.scale
+    d = types.SimpleNamespace(**dict(vars(data), obs=x, mean=None, scale=None))
+    r, _ = ratios(torch, d, data.theta)
+    assert float(torch.minimum((r[:m] - (1 + CLIP)).abs(), (r[:m] - (1 - CLIP)).abs()).min()) >= 1e-4
+    v = data.dev
+    P = dev_params(torch, data.theta)
+    got, st = env.ppo_grad(P, x[:m].to("cuda:0"), v.actions[:m], v.logp_old[:m], v.adv[:m], v.ret[:m], clip=CLIP,
+                           vf_coef=VF, ent_coef=ENT, obs_mean=None, obs_scale=None)
+    torch.cuda.synchronize()
+    rows = torch.arange(m)
+    ref = loss_on(torch, d, data.theta, rows, torch.float64) + loss_on(torch, d, data.theta, rows, torch.float32)
+    assert float(ref[0].abs().max()) > 1e-3
+    print()
+    check_values(torch, f"M={m}, no mean / scale", got.cpu(), st.cpu(), ref)
+    assert float(st[7]) == 0.0
+
+
+# Sizes past the kernels' own loop thresholds, reached with an index drawn with replacement from the B stored
+# rows.  tiles = ceil(M / 64); the gradient kernel runs nb = min(ceil(tiles / 4), 256) blocks of four waves, wave
+# w of block k taking the tiles 4 k + w, 4 k + w + 4 nb, ..; the reduce kernel's chain c adds the blocks c, c + 4,
+# .., sixteen at a time while b + 60 < nb and one at a time after that.
+#   M        tiles  nb
+#   15 361     241   61   chain 0 takes one batch of sixteen (0 + 60 < 61), chains 1-3 the one-by-one loop only
+#   16 384     256   64   every chain exactly one batch and nothing after it; every lane of every tile valid
+#   16 385     257   65   chain 0 a batch and one more term; block 64 is one wave with one valid lane
+#   33 000     516  129   two batches (b = c, c + 64: c + 124 < 129) and a term after them for chain 0
+#   65 666   1 027  256   the block cap: tiles 1024-1026 are the second trip of block 0's waves 0-2, the last one
+#                         with 2 valid lanes; four batches per chain and nothing after them
+#  131 139   2 050  256   every wave takes two tiles, waves 0 and 1 of block 0 a third (tiles 2048, 2049; 3 lanes)
+LARGE = (15361, 16384, 16385, 33000, 65666, 131139)
+OUT_OF_RANGE = (-1, B, 2 ** 31 - 1, -2 ** 31)
+
+
+def large_case(torch, d, m):
+    """A drawn index of m entries, the same with four entries that name no row, and the references; once per m."""
+    key = ("large", m)
+    if key not in d.refs:
+        g = torch.Generator().manual_seed(1000 + m)
+        clean = torch.randint(0, B, (m,), generator=g, dtype=torch.int64)
+        # where the four go: the first lane of all; the last lane of tile 1; a lane of tile 1024, a wave's second
+        # trip, where M reaches it (else of tile 5); the last entry (the last, ragged, tile's last valid lane)
+        where = [0, 127, 1024 * 64 + 35 if m > 1025 * 64 else 5 * 64 + 35, m - 1]
+        assert where[2] < m - 1
+        planted = clean.clone()
+        planted[where] = torch.tensor(OUT_OF_RANGE)
+        keep = torch.ones(m, dtype=torch.bool)
+        keep[where] = False
+        rows = clean[keep]
+        r, _ = ratios(torch, d, d.theta)
+        clipped_out = ((d.adv > 0) & (r > 1 + CLIP)) | ((d.adv < 0) & (r < 1 - CLIP))
+        outside = (r < 1 - CLIP) | (r > 1 + CLIP)
+        for ix in (clean, rows):
+            assert 0.10 <= float(clipped_out[ix].double().mean()) <= 0.60, m
+        ref, ref_clean = (loss_on(torch, d, d.theta, ix, torch.float64, divisor=m)
+                          + loss_on(torch, d, d.theta, ix, torch.float32, divisor=m) for ix in (rows, clean))
+        d.refs[key] = types.SimpleNamespace(clean=clean, planted=planted, rows=rows, ref=ref, ref_clean=ref_clean,
+                                            outside=int(outside[rows].sum()), outside_clean=int(outside[clean].sum()))
+    return d.refs[key]
+
+
+@pytest.mark.parametrize("m", LARGE)
+def test_large_index_values_and_exact_counts(torch, data, env, m):
+    """Values as test_values_against_float64; and two counts no tolerance covers: the rows whose ratio is outside
+    the clip range and the entries that name no row.  stats[3] is that count, an integer below 2^24 that float32
+    sums exactly, times the float32 1 / M: two roundings, so stats[3] * M is within count * 2^-22 < 0.04 of it.
+    Once with four entries out of range (the means still divide by M), once with every entry in range, so that
+    the last tile's last lane contributes."""
+    c = large_case(torch, data, m)
+    got, st = run(torch, env, data, data.theta, index=c.planted.to(torch.int32).to("cuda:0"))
+    print()
+    check_values(torch, f"M={m} by index, 4 out of range", got, st, c.ref)
+    assert float(st[7]) == len(OUT_OF_RANGE)
+    assert round(float(st[3]) * m) == c.outside, (float(st[3]) * m, c.outside)
+    # and with every entry in range (the last tile's lanes all count)
+    got, st = run(torch, env, data, data.theta, index=c.clean.to(torch.int32).to("cuda:0"))
+    check_values(torch, f"M={m} by index", got, st, c.ref_clean)
+    assert float(st[7]) == 0.0
+    assert round(float(st[3]) * m) == c.outside_clean, (float(st[3]) * m, c.outside_clean)
+
+
+def test_large_index_second_trip_is_bitwise_the_materialised_rows_and_deterministic(torch, data, env):
+    m = 65666   # 1 027 tiles on 256 blocks: the first three waves take a second tile, with and without an index
+    c = large_case(torch, data, m)
+    v = data.dev
+    ix = c.clean.to(torch.int32).to("cuda:0")
+    a, sa = run(torch, env, data, data.theta, index=ix)
+    b, sb = run(torch, env, data, data.theta, index=ix)
+    _assert_same(torch, a, b, "two calls")
+    _assert_same(torch, sa, sb, "two calls' stats")
+    P = dev_params(torch, data.theta)
+    di = c.clean.to("cuda:0")
+    gm, sm = env.ppo_grad(P, v.obs[di].contiguous(), v.actions[di].contiguous(), v.logp_old[di].contiguous(),
+                          v.adv[di].contiguous(), v.ret[di].contiguous(), clip=CLIP, vf_coef=VF, ent_coef=ENT,
+                          obs_mean=v.mean, obs_scale=v.scale)
+    torch.cuda.synchronize()
+    _assert_same(torch, a, gm.cpu(), "gradient")
+    _assert_same(torch, sa, sm.cpu(), "stats")
+    assert float(sa[7]) == 0.0 and round(float(sa[3]) * m) == c.outside_clean
 
 
 def test_index_is_bitwise_the_materialised_rows(torch, data, env):

@@ -1,8 +1,10 @@
 """GPU: the PPO update on the device (hg_ppo_shuffle, hg_ppo_adam, hg_ppo_update, hg_set_policy_theta and their
 HeliVecEnv wrappers).
 
-  1. the shuffle is the host restatement (tests/ppo_shuffle_ref.py), exactly, also keyed by a device counter;
-  2. the optimiser step's values against a float64 restatement, measured against CPU float32 torch Adam;
+  1. the shuffle is the host restatement (tests/ppo_shuffle_ref.py), exactly, also keyed by a device counter, at
+     sizes up to 262 144 and at an epoch past 2^32;
+  2. the optimiser step's values against a float64 restatement, measured against CPU float32 torch Adam, at step
+     counts 1 .. 6, 1 000 and 1 000 003;
   3. ppo_update is bitwise the calls it is made of, made one by one;
   4. determinism, and what must stay untouched does;
   5. a non-finite gradient is dropped and counted, the next clean one applied;
@@ -85,13 +87,19 @@ def by_hand(torch, env, d, P, S, rows, epochs, minibatches, seed, index, stats, 
 
 
 # ------------------------------------------------------------------------------------------- 1. shuffle
-@pytest.mark.parametrize("n", (1, 2, 3, 63, 64, 65, 4099))
+# 65 537: B - 1 has 17 bits, half = 9, the domain 4^9 = 262 144 just under 4 B (the longest cycle walks);
+# 262 144: B - 1 has 18 bits, half = 9, the domain is B itself (no element walks)
+@pytest.mark.parametrize("n", (1, 2, 3, 63, 64, 65, 4099, 65537, 262144))
 def test_shuffle_is_the_host_restatement(torch, env, n):
     seed = 0x9E3779B97F4A7C15
     got = env.ppo_shuffle(n, seed).cpu().numpy()
-    want, _ = shuffle_ref(n, seed, 0)
+    want, passes = shuffle_ref(n, seed, 0)
     assert got.dtype == np.int32 and np.array_equal(got, want)
     assert np.array_equal(np.sort(got), np.arange(n))
+    if n == 65537:
+        assert passes.max() > 8   # (three of four values of the domain are outside [0, B): long walks exist)
+    if n == 262144:
+        assert passes.max() == 1
 
 
 def test_shuffle_reads_its_epoch_on_the_device(torch, env):
@@ -104,6 +112,21 @@ def test_shuffle_reads_its_epoch_on_the_device(torch, env):
     assert np.array_equal(a.cpu().numpy(), shuffle_ref(n, seed, 5)[0])
     assert np.array_equal(c.cpu().numpy(), shuffle_ref(n, seed, 3)[0])
     assert not torch.equal(a, c)
+
+
+def test_shuffle_epoch_past_32_bits(torch, env):
+    """epoch = 2^32 + 3: the high word of the round function's epoch counter, e_hi, is 1, not 0; reached on the
+    host, and as 2^32 on the host plus 3 in the device word."""
+    seed, n = 77, 4099
+    big = 2 ** 32 + 3
+    want = shuffle_ref(n, seed, big)[0]
+    a = env.ppo_shuffle(n, seed, epoch=big).cpu().numpy()
+    three = torch.tensor([3], dtype=torch.int32, device=DEV)
+    b = env.ppo_shuffle(n, seed, epoch=2 ** 32, epoch_dev=three).cpu().numpy()
+    assert np.array_equal(a, want) and np.array_equal(b, want)
+    assert np.array_equal(np.sort(a), np.arange(n))
+    low = env.ppo_shuffle(n, seed, epoch=3).cpu().numpy()
+    assert np.array_equal(low, shuffle_ref(n, seed, 3)[0]) and not np.array_equal(a, low)
 
 
 # ------------------------------------------------------------------------------------------- 2. Adam values
@@ -190,6 +213,36 @@ def test_adam_values_against_float64(torch, data, env, clipped):
         assert (ref64[4] < 1.0) == clipped
         assert abs(c1["last_clip_coef"] - ref64[4]) <= 1e-6
         _assert_same(torch, P.grad.cpu(), g, "grad is not modified")
+
+
+@pytest.mark.parametrize("t0", (999, 1000002))
+def test_adam_values_at_a_working_step_count(torch, data, env, t0):
+    """One step from a state whose `applied` word says t0 steps were taken: beta^t by squaring takes 10 trips for
+    t = 1 000 = 0b1111101000 and 20 for t = 1 000 003 (six steps take 3), and the fp64 bias corrections are the
+    ones of a long run: 1 - 0.999^1000 = 0.632 at the first, both 1 to the last fp64 bit at the second."""
+    print()
+    P, S = fresh(torch, data)
+    for _ in range(3):   # m and v of a few real steps
+        env.ppo_grad(P, *rows_of(data, 4099), **loss_kw(data))
+        env.ppo_adam(P, S, lr=LR, betas=BETAS, eps=EPS, max_grad_norm=0.5)
+    env.ppo_grad(P, *rows_of(data, 4099), **loss_kw(data))
+    S.tail[0] = t0
+    g = P.grad.cpu()
+    max_norm = 0.5 * float(torch.sqrt((g.double() ** 2).sum()))
+    before = (P.theta.cpu(), S.m.cpu(), S.v.cpu())
+    assert float(before[1].abs().max()) > 0 and float(before[2].abs().max()) > 0
+    c0 = S.counters()
+    assert (c0["applied"], c0["seen"]) == (t0, 3)
+    env.ppo_adam(P, S, lr=LR, betas=BETAS, eps=EPS, max_grad_norm=max_norm)
+    c1 = S.counters()
+    assert (c1["applied"], c1["seen"], c1["stop"], c1["skipped_nonfinite"], c1["skipped_stopped"]) == (t0 + 1, 4, 0, 0, 0)
+    ref64 = adam_ref64(torch, *before, t0, g, LR, BETAS, EPS, max_norm)
+    ref32 = adam_torch32(torch, *before, t0, g, LR, BETAS, EPS, max_norm)
+    got = (P.theta.cpu(), S.m.cpu(), S.v.cpu(), c1["last_norm"])
+    assert float((got[0] - before[0]).abs().max()) > 0.1 * LR   # a real step
+    check_step(torch, f"step {t0 + 1}, clip coefficient {ref64[4]:.3f}", got, ref64, ref32)
+    assert ref64[4] < 1.0 and abs(c1["last_clip_coef"] - ref64[4]) <= 1e-6
+    _assert_same(torch, P.grad.cpu(), g, "grad is not modified")
 
 
 # ------------------------------------------------------------------------------------------- 3. composition
