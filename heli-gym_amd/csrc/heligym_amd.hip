@@ -28,6 +28,7 @@
 #include "retrim.h"
 #include "ppo_grad.h"
 #include "ppo_opt.h"
+#include "rollout_stats.h"
 #include "retrim_body.h"
 #include "baked.h"
 
@@ -3278,6 +3279,80 @@ int32_t hg_set_policy_theta(hg_env* e, const float* theta, const float* obs_mean
                                      stream);
     if (rc != HG_OK) return rc;
     return hg_set_value_head(e, theta + hgk::kPpoWv, theta + hgk::kPpoBv, stream);
+}
+
+// ---- running normalisation and episode statistics (the kernels: rollout_stats.hip)
+int64_t hg_rollout_stats_state_bytes(int64_t n_envs) {
+    if (n_envs < 1) return HG_E_INVALID;
+    return hgk::stats_state_bytes(n_envs);
+}
+
+static int32_t stats_state_check(const char* who, const hg_env* e, const void* state) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!state) return fail(HG_E_INVALID, std::string(who) + ": state must be a device pointer");
+    if ((uintptr_t)state & 15) return fail(HG_E_INVALID, std::string(who) + ": state must be 16-byte aligned");
+    return HG_OK;
+}
+
+int32_t hg_rollout_stats_init(hg_env* e, void* state, void* stream) {
+    const int32_t rc = stats_state_check("hg_rollout_stats_init", e, state);
+    if (rc != HG_OK) return rc;
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    HIP_TRY(hgk::launch_rollout_stats_zero(state, e->n, (hipStream_t)stream));
+    return HG_OK;
+}
+
+int32_t hg_rollout_stats(hg_env* e, void* state, const float* obs, const float* reward, const uint8_t* terminated,
+                         const uint8_t* truncated, const uint8_t* info, const float* obs0, int32_t nsteps,
+                         const hg_rollout_stats_cfg* cfg, float* obs_mean_out, float* obs_scale_out, float* reward_scale_out,
+                         float* reward_out, float* obs_in_out, float* episode_out, void* stream) {
+    const int32_t rc = stats_state_check("hg_rollout_stats", e, state);
+    if (rc != HG_OK) return rc;
+    if (!obs || !reward || !terminated || !truncated || !cfg)
+        return fail(HG_E_INVALID,
+                    "hg_rollout_stats: obs/reward/terminated/truncated must be device pointers, cfg a host pointer");
+    if ((((uintptr_t)obs | (uintptr_t)obs0 | (uintptr_t)obs_in_out) & 15) != 0)
+        return fail(HG_E_INVALID, "hg_rollout_stats: obs, obs0 and obs_in_out must be 16-byte aligned");
+    if ((((uintptr_t)reward | (uintptr_t)obs_mean_out | (uintptr_t)obs_scale_out | (uintptr_t)reward_scale_out |
+          (uintptr_t)reward_out | (uintptr_t)episode_out) & 3) != 0)
+        return fail(HG_E_INVALID, "hg_rollout_stats: every fp32 pointer must be 4-byte aligned");
+    if (nsteps < 1) return fail(HG_E_INVALID, "hg_rollout_stats: nsteps must be >= 1");
+    if (obs_in_out && !obs0) return fail(HG_E_INVALID, "hg_rollout_stats: obs_in_out needs obs0 (its first step's rows)");
+    if (reward_out && reward_out == reward) return fail(HG_E_INVALID, "hg_rollout_stats: reward_out must not be reward");
+    if (!(cfg->gamma >= 0.0) || !(cfg->gamma <= 1.0)) return fail(HG_E_INVALID, "hg_rollout_stats: gamma must be in [0, 1]");
+    if (!(cfg->obs_eps >= 0.0) || !(cfg->ret_eps >= 0.0) || std::isinf(cfg->obs_eps) || std::isinf(cfg->ret_eps))
+        return fail(HG_E_INVALID, "hg_rollout_stats: obs_eps and ret_eps must be finite and >= 0");
+    if (!(cfg->max_obs_scale > 0.f) || !(cfg->clip_reward > 0.f))
+        return fail(HG_E_INVALID, "hg_rollout_stats: max_obs_scale and clip_reward must be > 0 (+inf: off)");
+    if (cfg->update & ~(uint32_t)(HG_STATS_UPDATE_OBS | HG_STATS_UPDATE_RET))
+        return fail(HG_E_INVALID, "hg_rollout_stats: unknown update bits");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    hgk::RolloutStatsArgs a;
+    a.state = state;
+    a.obs = obs;
+    a.reward = reward;
+    a.terminated = terminated;
+    a.truncated = truncated;
+    a.info = info;
+    a.obs0 = obs0;
+    a.n = e->n;
+    a.nsteps = nsteps;
+    a.gamma = (float)cfg->gamma;
+    a.obs_eps = cfg->obs_eps;
+    a.ret_eps = cfg->ret_eps;
+    a.max_obs_scale = cfg->max_obs_scale;
+    a.clip_reward = cfg->clip_reward;
+    a.update = cfg->update;
+    a.obs_mean_out = obs_mean_out;
+    a.obs_scale_out = obs_scale_out;
+    a.reward_scale_out = reward_scale_out;
+    a.reward_out = reward_out;
+    a.obs_in_out = obs_in_out;
+    a.episode_out = episode_out;
+    HIP_TRY(hgk::launch_rollout_stats(a, (hipStream_t)stream));
+    return HG_OK;
 }
 
 // The planning calls check their plain arguments before the handle, so that a bad one is refused with

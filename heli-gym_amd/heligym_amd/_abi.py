@@ -86,6 +86,15 @@ class hg_ppo_opt_cfg(ctypes.Structure):
                 ("target_kl", ctypes.c_float)]
 
 
+HG_STATS_UPDATE_OBS, HG_STATS_UPDATE_RET = 1, 2
+
+
+class hg_rollout_stats_cfg(ctypes.Structure):
+    _fields_ = [("gamma", ctypes.c_double), ("obs_eps", ctypes.c_double), ("ret_eps", ctypes.c_double),
+                ("max_obs_scale", ctypes.c_float), ("clip_reward", ctypes.c_float), ("update", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
 # Every symbol include/heligym_amd.h declares, with its ctypes signature.
 _P = ctypes.c_void_p
 _SIGS = {
@@ -131,6 +140,10 @@ _SIGS = {
                                        ctypes.c_float, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, _P, _P, _P,
                                        ctypes.POINTER(hg_ppo_opt_cfg), _P]),
     "hg_set_policy_theta": (ctypes.c_int32, [_P, _P, _P, _P, _P]),
+    "hg_rollout_stats_state_bytes": (ctypes.c_int64, [ctypes.c_int64]),
+    "hg_rollout_stats_init": (ctypes.c_int32, [_P, _P, _P]),
+    "hg_rollout_stats": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int32,
+                                          ctypes.POINTER(hg_rollout_stats_cfg), _P, _P, _P, _P, _P, _P, _P]),
     "hg_rollout_branch": (ctypes.c_int32, [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _P, _P,
                                            _P, _P]),
     "hg_mppi_sample": (ctypes.c_int32, [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float),

@@ -904,6 +904,77 @@ class HeliVecEnv(*_VEC_BASES):
             self.set_policy_theta(params, mean, scale)
         return st
 
+    # ------------------------------------------------------------------ running normalisation, episode statistics
+    def rollout_stats(self, stats, rollout, gamma=0.99, obs0=None, obs_in=None, reward_out=None, update_obs=True,
+                      update_ret=True, obs_eps=1e-8, ret_eps=1e-8, max_obs_scale=None, clip_reward=None):
+        """Running normalisation and episode statistics of one rollout (hg_rollout_stats; the function is
+        heligym_amd.stats.rollout_stats_ref).  stats: a RolloutStats of this env; rollout: what
+        rollout_actor_critic (a dict) or rollout_policy (a tuple) returned, read as it is.  Updates the running
+        moments of the observations and of the discounted return (gamma) and the per-env episode return /
+        length, which persist from call to call, and fills stats.obs_mean / obs_scale (float32 [17], from the
+        moments AFTER this batch: the next collection's normalisation), stats.reward_scale [1] and
+        stats.episode [16] (stats.EPISODE_FIELDS: episodes completed in this call, their return's mean / std /
+        min / max, mean length, terminated / truncated / success counts, ...).
+        reward_out: a float32 [K,N] tensor (not the rollout's reward) for clamp(reward * reward_scale,
+        +-clip_reward).  obs_in: a float32 [K,N,17] tensor for the observations the actions were computed from
+        (obs0, obs[0], .., obs[K-2]), with obs0 [N,17], the rollout's start.  update_obs / update_ret False
+        freeze that part (evaluation); max_obs_scale / clip_reward None: unbounded.  Returns `stats`.
+        Asynchronous on the current stream, allocates nothing, capturable; the env is not modified."""
+        import math
+        from . import stats as _stats
+        t = self.torch
+        who = "rollout_stats"
+        if not isinstance(stats, _stats.RolloutStats):
+            raise ValueError(f"{who}: stats must be a RolloutStats, got {type(stats).__name__}")
+        if isinstance(rollout, dict):
+            try:
+                obs, rew, term, trunc = (rollout[k] for k in ("obs", "reward", "terminated", "truncated"))
+            except KeyError as e:
+                raise ValueError(f"{who}: rollout has no {e.args[0]!r}") from None
+            info = rollout.get("info")
+        elif isinstance(rollout, (tuple, list)) and len(rollout) == 6:
+            _, obs, rew, term, trunc, info = rollout
+        else:
+            raise ValueError(f"{who}: rollout must be rollout_actor_critic's dict or rollout_policy's tuple of six")
+        if not isinstance(rew, t.Tensor) or rew.ndim != 2 or rew.shape[0] < 1:
+            raise ValueError(f"{who}: reward must be a [K, N] tensor")
+        K, N = int(rew.shape[0]), self.num_envs
+        state = self._opt_tensor(stats.state, (_stats.stats_state_bytes(N) // 4,), "stats.state", t.int32, who)
+        o = self._opt_tensor(obs, (K, N, _abi.HG_N_OBS), "obs", who=who)
+        r = self._opt_tensor(rew, (K, N), "reward", who=who)
+        te = self._opt_tensor(term, (K, N), "terminated", t.uint8, who)
+        tr = self._opt_tensor(trunc, (K, N), "truncated", t.uint8, who)
+        inf = None if info is None else self._opt_tensor(info, (K, N), "info", t.uint8, who)
+        if obs_in is not None and obs0 is None:
+            raise ValueError(f"{who}: obs_in needs obs0, the observations the rollout started from")
+        o0 = None if obs0 is None else self._opt_tensor(obs0, (N, _abi.HG_N_OBS), "obs0", who=who)
+        oi = None if obs_in is None else self._opt_tensor(obs_in, (K, N, _abi.HG_N_OBS), "obs_in", who=who)
+        ro = None if reward_out is None else self._opt_tensor(reward_out, (K, N), "reward_out", who=who)
+        if ro is not None and (ro is r or ro.data_ptr() == r.data_ptr()):
+            raise ValueError(f"{who}: reward_out must not be the rollout's reward")
+        outs = [self._opt_tensor(getattr(stats, k), s, f"stats.{k}", who=who)
+                for k, s in (("obs_mean", (_abi.HG_N_OBS,)), ("obs_scale", (_abi.HG_N_OBS,)), ("reward_scale", (1,)),
+                             ("episode", (16,)))]
+        try:
+            gamma, obs_eps, ret_eps = float(gamma), float(obs_eps), float(ret_eps)
+            mos = math.inf if max_obs_scale is None else float(max_obs_scale)
+            clip = math.inf if clip_reward is None else float(clip_reward)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: gamma, the eps, max_obs_scale and clip_reward must be numbers") from None
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError(f"{who}: gamma must be in [0, 1], got {gamma}")
+        if not (0.0 <= obs_eps < math.inf and 0.0 <= ret_eps < math.inf):
+            raise ValueError(f"{who}: obs_eps and ret_eps must be finite and >= 0, got {(obs_eps, ret_eps)}")
+        if not (mos > 0.0 and clip > 0.0):
+            raise ValueError(f"{who}: max_obs_scale and clip_reward must be > 0, got {(mos, clip)}")
+        update = (_abi.HG_STATS_UPDATE_OBS if update_obs else 0) | (_abi.HG_STATS_UPDATE_RET if update_ret else 0)
+        cfg = _abi.hg_rollout_stats_cfg(gamma, obs_eps, ret_eps, mos, clip, update, 0)
+        self._keep_stats = (state, o, r, te, tr, inf, o0, oi, ro, outs)
+        self._check(self.lib.hg_rollout_stats(self._h, _ptr(state), _ptr(o), _ptr(r), _ptr(te), _ptr(tr), _ptr(inf),
+                                              _ptr(o0), K, ctypes.byref(cfg), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
+                                              _ptr(ro), _ptr(oi), _ptr(outs[3]), self._stream()))
+        return stats
+
     # ------------------------------------------------------------------ branched planning rollouts
     def _plan_tensor(self, x, shape, name, dtype=None):
         """`x` as the library reads it: a contiguous tensor of `shape` and `dtype` on the env's device

@@ -513,6 +513,102 @@ int32_t hg_ppo_update(hg_env* env, float* theta_dev, const float* obs_mean_dev, 
 int32_t hg_set_policy_theta(hg_env* env, const float* theta_dev, const float* obs_mean_dev, const float* obs_scale_dev,
                             void* stream);
 
+/* ---- Running normalisation and episode statistics: one pass over what a rollout wrote.
+ *
+ * What SB3's VecNormalize / gymnasium's NormalizeObservation + NormalizeReward and an episode monitor keep,
+ * kept on the device across calls: running moments of the observations and of the discounted return, per-env
+ * return and length accumulators that survive the end of a K-step launch, and the aggregates of the episodes
+ * that ended in this one.  Asynchronous on `stream`, allocates nothing, capturable.  The env is not modified:
+ * it is used for N, its device and the error convention, as in hg_gae.
+ *
+ * Inputs, a rollout's outputs as they are (N the env's): obs_dev [nsteps,N,17] fp32, reward_dev [nsteps,N]
+ * fp32, terminated_dev / truncated_dev [nsteps,N] u8; info_dev [nsteps,N] u8 or NULL (the success count is
+ * then 0); obs0_dev [N,17], the observations the rollout started from, required iff obs_in_out_dev is given.
+ *
+ * State: hg_rollout_stats_state_bytes(n_envs) bytes of device memory, 16-byte aligned, owned by the caller
+ * (byte offset: content):
+ *        0: an fp64 head of 48 doubles (double index: content):
+ *             0: obs_count              rows that entered the observation moments
+ *             1: obs_mean [17]
+ *            18: obs_M2 [17]            sum of squared deviations: the population variance is M2 / count
+ *            35: ret_count              samples of G that entered the return moments
+ *            36: ret_mean
+ *            37: ret_M2
+ *            38: episodes               lifetime total of completed episodes
+ *            39: env_steps              lifetime total of env-steps
+ *            40: skipped_rows           lifetime total of observation rows left out (a non-finite value)
+ *            41: skipped_returns        lifetime total of return samples left out (non-finite)
+ *            42 .. 47                   reserved, zero
+ *      384: G [N] fp32, each env's discounted return so far
+ *   384 + 4 N: ep_ret [N] fp32, the running episode's return
+ *   384 + 8 N: ep_len [N] i32, its length
+ *   384 + 12 N, rounded up to a multiple of 16: a workspace of 180240 bytes for the kernels' partial sums,
+ *             its contents irrelevant between calls.
+ * hg_rollout_stats_init zeroes all of it (one kernel, not a memset).
+ *
+ * Per env n, for k = 0 .. nsteps-1, in this order (fp32; gamma is the configuration's, rounded to fp32 once):
+ *   1. G = fma(gamma, G, reward[k,n]); the sample G enters the return moments.
+ *   2. ep_ret = ep_ret + reward[k,n];  ep_len = ep_len + 1.
+ *   3. If terminated[k,n] | truncated[k,n]: the episode (ep_ret, ep_len, terminated[k,n] != 0,
+ *      info[k,n] & HG_INFO_SUCCESSED) enters this call's episode aggregates, then G, ep_ret and ep_len are set
+ *      to 0 (by assignment: a NaN does not survive its episode's end).
+ * Observation moments: over all nsteps * N rows of obs_dev, per column, population moments.  The batch is
+ * accumulated in fp64 as shifted sums, sum (x - c) and sum (x - c)^2, with c the state's mean when obs_count
+ * > 0 and otherwise the row obs[0,0,:] (a non-finite value of it replaced by 0), and merged into the state
+ * by Chan's update; the return moments likewise, with c the state's ret_mean or 0.  A row with any non-finite
+ * value is left out of all 17 columns and counted; a non-finite sample of G is left out of the return moments
+ * and counted (G, ep_ret carry what the arithmetic gives until the episode's end clears them); an episode
+ * whose return is not finite is counted, with its length and flags, but left out of the return statistics.
+ * Nothing non-finite ever enters the head.
+ *
+ * Outputs, each or NULL, all from the state AFTER this call's merge (SB3's order):
+ *   obs_mean_out_dev [17]     (float)obs_mean
+ *   obs_scale_out_dev [17]    min((float)(1 / sqrt(obs_M2 / obs_count + obs_eps)), max_obs_scale), fp64 rounded once
+ *   reward_scale_out_dev [1]  (float)(1 / sqrt(ret_M2 / ret_count + ret_eps))
+ *   reward_out_dev [nsteps,N] clamp(reward * reward_scale, +-clip_reward): one fp32 multiply, a NaN stays a NaN;
+ *                             must not be reward_dev
+ *   obs_in_out_dev [nsteps,N,17]  the observations the actions were computed from: obs_in[0] = obs0,
+ *                             obs_in[k] = obs[k-1], bitwise
+ *   episode_out_dev [16] fp32 [0] episodes completed in this call  [1] mean, [2] population standard deviation,
+ *                             [3] min, [4] max of their returns  [5] their mean length  [6] of them terminated
+ *                             [7] truncated only  [8] with HG_INFO_SUCCESSED  [9] mean finite reward per step of
+ *                             the batch  [10] observation rows, [11] return samples left out in this call
+ *                             [12] episodes with a non-finite return (left out of [1] .. [4])  [13] .. [15] zero.
+ *                             Without a completed episode [1] .. [5] are NaN and the counts 0.
+ * With a count of 0 the mean is 0 and the scales are 1.
+ *
+ * cfg.update: a cleared bit freezes that part of the head and the outputs come from the state as it stands
+ * (evaluation).  HG_STATS_UPDATE_OBS: the observation moments and skipped_rows; HG_STATS_UPDATE_RET: the
+ * return moments and skipped_returns; episodes and env_steps advance when either bit is set.  The per-env
+ * scans and the episode aggregates always run.
+ *
+ * Deterministic: no atomics; the launch shapes depend on (nsteps, N) and compile-time constants only and the
+ * partial sums are added in a fixed order (csrc/rollout_stats.hip states it): two calls on the same inputs
+ * and state give the same bits.
+ * HG_E_INVALID, outputs and state untouched: NULL env; NULL state_dev, obs_dev, reward_dev, terminated_dev,
+ * truncated_dev or cfg; a misaligned pointer (state_dev, obs_dev, obs0_dev, obs_in_out_dev 16 bytes, the other
+ * fp32 pointers 4); nsteps < 1; obs_in_out_dev without obs0_dev; reward_out_dev == reward_dev; gamma outside
+ * [0, 1] or NaN; a negative or NaN eps; max_obs_scale or clip_reward NaN or <= 0; unknown update bits. */
+enum { HG_STATS_UPDATE_OBS = 1, HG_STATS_UPDATE_RET = 2 };
+
+typedef struct hg_rollout_stats_cfg {
+    double gamma;          /* the discount of G, in [0, 1] */
+    double obs_eps;        /* added to the observation variance under the square root, >= 0 */
+    double ret_eps;        /* added to the return variance under the square root, >= 0 */
+    float max_obs_scale;   /* upper bound of obs_scale; +inf: off */
+    float clip_reward;     /* bound of |reward_out|; +inf: off */
+    uint32_t update;       /* HG_STATS_UPDATE_* bits */
+    uint32_t reserved;     /* zero */
+} hg_rollout_stats_cfg;
+
+int64_t hg_rollout_stats_state_bytes(int64_t n_envs);   /* a multiple of 16; negative for n_envs < 1; host only */
+int32_t hg_rollout_stats_init(hg_env* env, void* state_dev, void* stream);
+int32_t hg_rollout_stats(hg_env* env, void* state_dev, const float* obs_dev, const float* reward_dev,
+                         const uint8_t* terminated_dev, const uint8_t* truncated_dev, const uint8_t* info_dev,
+                         const float* obs0_dev, int32_t nsteps, const hg_rollout_stats_cfg* cfg, float* obs_mean_out_dev,
+                         float* obs_scale_out_dev, float* reward_scale_out_dev, float* reward_out_dev,
+                         float* obs_in_out_dev, float* episode_out_dev, void* stream);
+
 /* ---- Branched planning rollouts: many candidate action sequences per env, scored without touching it.
  *
  * What a receding-horizon sampling planner (MPPI, CEM, random shooting) needs from the rollout: `branches`
