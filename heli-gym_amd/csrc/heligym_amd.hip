@@ -410,6 +410,15 @@ struct BranchArgs {
     float gamma = 1.f;
 };
 
+// hg_rollout_branch_policy's arguments beside StepArgs, PolicyArgs (pk, obs0) and BranchArgs; all wave-uniform.
+// A struct of its own once more: no existing kernel's argument segment moves.
+struct BranchPolicyArgs {
+    const float* residual = nullptr;   // [nsteps, N*branches, 4] added to the policy's mean, or NULL
+    hgp::ActBox box = {};              // the applied action's bounds
+    int32_t bootstrap = 0;             // HG_BOOTSTRAP_VALUE: survivors and truncated rows add disc * value_scale * V(o')
+    float value_scale = 1.f;
+};
+
 // TASK: reward / success of the task; ETA: noise injected by the caller (else in-kernel Philox);
 // NT: streaming output stores (see st_out); FEAT: the optional features (reset-info compaction,
 // per-reset re-trim, next-step auto-reset, TimeLimit) -- without them the kernel carries none of
@@ -433,16 +442,23 @@ struct BranchArgs {
 // from that env's tile slot and nobody writes back.  A row is stepped as above up to its first ending
 // step and never reset; nothing is stored per step, the discounted return, the step count and the
 // ending step's info bits once at the end.  ETA here means no noise (eta = 0), not injected noise.
+// BRANCH with POLICY (hg_rollout_branch_policy): the row's action is the policy's mean of the row's own
+// observation -- its env's row of pol.obs0 at the first step -- plus bp.residual's row, clamped
+// (hgp::residual_action).  One hgp::policy_eval(sample = false) per iteration gives that mean and V of the
+// same observation, which is the bootstrap term of a row the previous step truncated and, in one more
+// iteration that leaves before the step, of the rows that survived the horizon.
 template <int TASK, bool ETA, bool NT, bool FEAT, bool MULTI, bool BAKED, bool NTS, int HELP = 0, bool POLICY = false,
           bool AC = false, bool BRANCH = false>
 __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p,
                                           ParamArg Pa, const Template<float>* __restrict__ Tp, const StepArgs& a,
                                           int64_t bid, const PolicyArgs& pol = PolicyArgs{}, const AcArgs& ac = AcArgs{},
-                                          const BranchArgs& br = BranchArgs{}) {
+                                          const BranchArgs& br = BranchArgs{},
+                                          const BranchPolicyArgs& bp = BranchPolicyArgs{}) {
     static_assert(HELP == 0 || (!ETA && !MULTI), "wind helper waves: in-kernel noise, one step per launch");
     static_assert(!POLICY || (MULTI && HELP == 0), "the in-kernel policy belongs to the rollout");
     static_assert(!AC || POLICY, "log-probabilities and values are the in-kernel policy's");
-    static_assert(!BRANCH || (MULTI && FEAT && HELP == 0 && !POLICY), "branched rollouts: the open-loop rollout's steps");
+    static_assert(!BRANCH || (MULTI && FEAT && HELP == 0 && !AC), "branched rollouts: the rollout's steps");
+    static_assert(!(BRANCH && POLICY) || NT, "policy-guided branches: one wave per SIMD, the lone-wave step");
     // the policy's matrix products take the wave's 64 envs as their columns: a block is one wave
     static_assert(!POLICY || kStepBlock == 64, "hg_rollout_policy needs one-wave step blocks (HG_STEP_BLOCK 64)");
     __shared__ float s_obs[(HELP ? HELP * 64 : kStepBlock) * HG_N_OBS];   // one 64-row slice per wave
@@ -623,14 +639,18 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
     float pobs[POLICY ? 17 : 1];
     if constexpr (POLICY) {
         hgp::load_weights(pol.pk, lane, pw);
-        const float* row = pol.obs0 + (blk0 + lo) * 17;
+        // (BRANCH: the row's env's observation, as its state groups above)
+        const float* row = pol.obs0 + (BRANCH ? (int64_t)b_env : blk0 + lo) * 17;
 #pragma unroll
         for (int c = 0; c < 17; ++c) pobs[c] = row[c];
     }
     // AC: whether the previous step reset the lane (its next_value is stored already) or terminated it
     bool ac_prev_reset = false, ac_prev_term = false;
     // (AC with values: one more pass after the last step, which only evaluates the last observation)
-    const int niter = AC ? nsteps + (ac.next_value ? 1 : 0) : nsteps;
+    // (BRANCH with POLICY and a bootstrap: the same, for the survivors' V(o_H))
+    const int niter = AC ? nsteps + (ac.next_value ? 1 : 0) : ((BRANCH && POLICY) ? nsteps + (bp.bootstrap ? 1 : 0) : nsteps);
+    // BRANCH with POLICY: the row's last step truncated it without terminating it: its V(o') is due
+    bool bp_pend = false;
     for (int sstep = 0; sstep < niter; ++sstep) {
     // MULTI: the constants are re-read (scalar cache) each step rather than kept live across the
     // loop, where ~130 of them would spill out of the SGPR file
@@ -651,6 +671,17 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
             if (ac.logp) st_lane<kNTS>(ac.logp + so + blk0, (uint32_t)tid, ev.logp);
             if (ac.value) st_lane<kNTS>(ac.value + so + blk0, (uint32_t)tid, ev.v);
         }
+    } else if constexpr (BRANCH && POLICY) {
+        const hgp::Eval ev = hgp::policy_eval(pw, pol.pk, pobs, lane, seed_p, 0, 0, 0, false);
+        if (bp.bootstrap) {   // (uniform) br_disc here is the discount after the previous step's multiply
+            const bool boot = bp_pend || (sstep == nsteps && br_alive);
+            br_G = boot ? fmaf(br_disc, bp.value_scale * ev.v, br_G) : br_G;
+            bp_pend = false;
+        }
+        if (sstep == nsteps || !__any(br_alive)) break;   // (wave-uniform)
+        float4 res = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (bp.residual) res = ld_lane(reinterpret_cast<const float4*>(bp.residual) + so + blk0, lo);
+        act = hgp::residual_action(ev.a, res, bp.residual != nullptr, bp.box);
     } else if constexpr (POLICY) {
         act = hgp::policy_action(pw, pol.pk, pobs, lane, seed_p, (uint64_t)(envoff_p + blk0 + lo), step, epi);
         if (active)
@@ -784,8 +815,14 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
         br_end = (br_alive && done) ? (uint32_t)((failed ? HG_INFO_FAILED : 0) | (successed ? HG_INFO_SUCCESSED : 0) |
                                                  (time_up ? HG_INFO_TIME_UP : 0) | (success_step ? HG_INFO_SUCCESS_STEP : 0))
                                     : br_end;
+        if constexpr (POLICY) bp_pend = bp.bootstrap && br_alive && trunc && !term;
         br_alive = br_alive && !done;
-        if (!__any(br_alive)) break;   // (wave-uniform)
+        // (wave-uniform; POLICY: a lane's pending bootstrap takes the next iteration's forward pass)
+        if (!__any(POLICY ? (br_alive || bp_pend) : br_alive)) break;
+        if constexpr (POLICY) {
+#pragma unroll
+            for (int c = 0; c < 17; ++c) pobs[c] = obs[c];
+        }
         carry[0] = obs[4];
         carry[1] = obs[5];
         carry[2] = obs[6];
@@ -1111,6 +1148,21 @@ __global__ __launch_bounds__(kStepBlock, WAVES) void rollout_branch_kernel(
     static_assert(WAVES >= 1 && WAVES <= 3, "WAVES 1, 2: the lone-wave step; 3: the bulk step");
     step_body<TASK, NOISE_OFF, (WAVES < 3), true, true, BAKED, false, 0, false, false, true>(
         state_p, rows_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, PolicyArgs{}, AcArgs{}, br);
+}
+
+// hg_rollout_branch_policy: rollout_branch_kernel's rows with the handle's policy inside them (step_body's
+// BRANCH with POLICY): a closed-loop candidate a_t = clamp(mu(o_t) + residual[t, r]) and, on request, the
+// value head's V as the tail of the rows the horizon or a truncation cut.  One wave per block and per SIMD
+// for rollout_policy_kernel's reason -- the weights stay in registers across the steps -- and the
+// lone-wave step; rows past one wave per SIMD run as further blocks.  The bootstrap, the clamp and a
+// missing residual are wave-uniform run-time arguments, not template flags.
+template <int TASK, bool NOISE_OFF, bool BAKED>
+__global__ __launch_bounds__(64, 1) void rollout_branch_policy_kernel(
+    float* __restrict__ state_p, int64_t rows_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
+    const Template<float>* __restrict__ Tp, const StepArgs a, const PolicyArgs pol, const BranchArgs br,
+    const BranchPolicyArgs bp) {
+    step_body<TASK, NOISE_OFF, true, true, true, BAKED, false, 0, true, false, true>(
+        state_p, rows_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, pol, AcArgs{}, br, bp);
 }
 
 // hg_mppi_sample: candidate action sequences around a nominal one, element-wise over [horizon, N*branches]:
@@ -1593,6 +1645,32 @@ __global__ __launch_bounds__(64, 1) void policy_eval_kernel(const float* __restr
     if (!active) return;
     if (actions) reinterpret_cast<float4*>(actions)[i] = ev.a;
     if (logp) logp[i] = ev.logp;
+    if (value) value[i] = ev.v;
+}
+
+// hg_policy_act_mean: the action of a policy-guided branch for the given observation rows -- the policy's
+// mean (nothing drawn, so no counters are read), the residual row and the clamp through
+// hgp::residual_action, the function hg_rollout_branch_policy's kernels call -- and V(obs).
+__global__ __launch_bounds__(64, 1) void policy_act_mean_kernel(int64_t n, const float* __restrict__ pk,
+                                                                const float* __restrict__ obs,
+                                                                const float4* __restrict__ residual, const hgp::ActBox box,
+                                                                float4* actions, float* value) {
+    const int lane = threadIdx.x;
+    const int64_t blk0 = (int64_t)blockIdx.x * 64;
+    const bool active = blk0 + lane < n;
+    const int64_t i = blk0 + (active ? lane : 0);
+    hgp::Weights pw;
+    hgp::load_weights(pk, lane, pw);
+    float o[17];
+#pragma unroll
+    for (int c = 0; c < 17; ++c) o[c] = obs[i * 17 + c];
+    const hgp::Eval ev = hgp::policy_eval(pw, pk, o, lane, 0, 0, 0, 0, false);
+    if (!active) return;
+    if (actions) {
+        float4 res = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (residual) res = residual[i];
+        actions[i] = hgp::residual_action(ev.a, res, residual != nullptr, box);
+    }
     if (value) value[i] = ev.v;
 }
 
@@ -2280,6 +2358,31 @@ static void dispatch_rollout_branch(const hg_env* e, hipStream_t s, const StepAr
         case HG_TASK_HOVER: launch_rollout_branch<HG_TASK_HOVER>(e, s, a, br, rows, noise_off); break;
         case HG_TASK_FORWARD_FLIGHT: launch_rollout_branch<HG_TASK_FORWARD_FLIGHT>(e, s, a, br, rows, noise_off); break;
         default: launch_rollout_branch<HG_TASK_HELI>(e, s, a, br, rows, noise_off); break;
+    }
+}
+
+// hg_rollout_branch_policy's launch, as hg_rollout_policy's: task x noise mode x the constant-specialised
+// step when the env uses it, one-wave blocks over the rows
+template <int T>
+static void launch_rollout_branch_policy(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol,
+                                         const BranchArgs& br, const BranchPolicyArgs& bp, int64_t rows, bool noise_off) {
+    const unsigned grid = (unsigned)((rows + 63) / 64);
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, e->state, rows, (uint64_t)e->cfg.seed,
+                           (int64_t)e->cfg.env_offset, PARAM_ARG(e), e->tmpl_dev, a, pol, br, bp);
+    };
+    ++e->n_launch[4];
+    if (e->baked) noise_off ? go(rollout_branch_policy_kernel<T, true, true>) : go(rollout_branch_policy_kernel<T, false, true>);
+    else noise_off ? go(rollout_branch_policy_kernel<T, true, false>) : go(rollout_branch_policy_kernel<T, false, false>);
+}
+static void dispatch_rollout_branch_policy(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol,
+                                           const BranchArgs& br, const BranchPolicyArgs& bp, int64_t rows, bool noise_off) {
+    switch (e->cfg.task) {
+        case HG_TASK_HOVER: launch_rollout_branch_policy<HG_TASK_HOVER>(e, s, a, pol, br, bp, rows, noise_off); break;
+        case HG_TASK_FORWARD_FLIGHT:
+            launch_rollout_branch_policy<HG_TASK_FORWARD_FLIGHT>(e, s, a, pol, br, bp, rows, noise_off);
+            break;
+        default: launch_rollout_branch_policy<HG_TASK_HELI>(e, s, a, pol, br, bp, rows, noise_off); break;
     }
 }
 
@@ -3399,6 +3502,90 @@ int32_t hg_rollout_branch(hg_env* e, const float* actions, int32_t horizon, int3
     br.branches = (uint32_t)branches;
     br.gamma = gamma;
     dispatch_rollout_branch(e, (hipStream_t)stream, a, br, rows, noise_mode == HG_BRANCH_NOISE_OFF);
+    HIP_TRY(hipGetLastError());
+    return HG_OK;
+}
+
+// the applied action's bounds: both NULL (no clamp) or both host arrays of 4 with lo <= hi (a NaN fails it)
+static int32_t act_box(const char* who, const float lo[4], const float hi[4], hgp::ActBox* box) {
+    memset(box, 0, sizeof(*box));
+    if ((lo == nullptr) != (hi == nullptr))
+        return fail(HG_E_INVALID, std::string(who) + ": lo and hi go together (both host arrays of 4, or both NULL)");
+    if (!lo) return HG_OK;
+    for (int c = 0; c < 4; ++c) {
+        if (!(lo[c] <= hi[c])) return fail(HG_E_INVALID, std::string(who) + ": lo must be <= hi");
+        box->lo[c] = lo[c];
+        box->hi[c] = hi[c];
+    }
+    box->clamp = 1;
+    return HG_OK;
+}
+
+int32_t hg_policy_act_mean(hg_env* e, const float* obs, const float* residual, const float lo[4], const float hi[4],
+                           float* actions, float* value, void* stream) {
+    hgp::ActBox box;
+    if (act_box("hg_policy_act_mean", lo, hi, &box) != HG_OK) return HG_E_INVALID;
+    if (!obs) return fail(HG_E_INVALID, "hg_policy_act_mean: obs must be a device pointer");
+    if (((uintptr_t)residual & 15) || ((uintptr_t)actions & 15))
+        return fail(HG_E_INVALID, "hg_policy_act_mean: residual and actions must be 16-byte aligned");
+    if ((uintptr_t)value & 3) return fail(HG_E_INVALID, "hg_policy_act_mean: value must be 4-byte aligned");
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!e->policy_set) return fail(HG_E_INVALID, "hg_policy_act_mean: no policy set (hg_set_policy)");
+    if (value && !e->value_set)
+        return fail(HG_E_INVALID, "hg_policy_act_mean: value needs a value head (hg_set_value_head)");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    hipLaunchKernelGGL(policy_act_mean_kernel, dim3((unsigned)((e->n + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
+                       (int64_t)e->n, (const float*)e->policy_dev, obs, reinterpret_cast<const float4*>(residual), box,
+                       reinterpret_cast<float4*>(actions), value);
+    HIP_TRY(hipGetLastError());
+    return HG_OK;
+}
+
+int32_t hg_rollout_branch_policy(hg_env* e, const float* obs0, const float* residual, int32_t horizon, int32_t branches,
+                                 float gamma, int32_t noise_mode, const float lo[4], const float hi[4], int32_t bootstrap,
+                                 float value_scale, float* ret, int32_t* alive_steps, uint8_t* end_info, void* stream) {
+    const char* who = "hg_rollout_branch_policy";
+    if (branch_shape(who, horizon, branches) != HG_OK) return HG_E_INVALID;
+    if (!std::isfinite(gamma) || !(gamma > 0.f) || gamma > 1.f)
+        return fail(HG_E_INVALID, "hg_rollout_branch_policy: gamma must be in (0, 1]");
+    if (noise_mode != HG_BRANCH_NOISE_ENV && noise_mode != HG_BRANCH_NOISE_OFF)
+        return fail(HG_E_INVALID, "hg_rollout_branch_policy: noise_mode must be HG_BRANCH_NOISE_ENV or HG_BRANCH_NOISE_OFF");
+    if (bootstrap != HG_BOOTSTRAP_NONE && bootstrap != HG_BOOTSTRAP_VALUE)
+        return fail(HG_E_INVALID, "hg_rollout_branch_policy: bootstrap must be HG_BOOTSTRAP_NONE or HG_BOOTSTRAP_VALUE");
+    if (!std::isfinite(value_scale)) return fail(HG_E_INVALID, "hg_rollout_branch_policy: value_scale must be finite");
+    BranchPolicyArgs bp;
+    if (act_box(who, lo, hi, &bp.box) != HG_OK) return HG_E_INVALID;
+    if (!obs0 || !ret) return fail(HG_E_INVALID, "hg_rollout_branch_policy: obs0/return must be device pointers");
+    if ((uintptr_t)residual & 15) return fail(HG_E_INVALID, "hg_rollout_branch_policy: residual must be 16-byte aligned");
+    if (((uintptr_t)obs0 & 3) || ((uintptr_t)ret & 3) || ((uintptr_t)alive_steps & 3))
+        return fail(HG_E_INVALID, "hg_rollout_branch_policy: obs0, return and alive_steps must be 4-byte aligned");
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!e->policy_set) return fail(HG_E_INVALID, "hg_rollout_branch_policy: no policy set (hg_set_policy)");
+    if (bootstrap == HG_BOOTSTRAP_VALUE && !e->value_set)
+        return fail(HG_E_INVALID, "hg_rollout_branch_policy: bootstrap HG_BOOTSTRAP_VALUE needs a value head (hg_set_value_head)");
+    int64_t rows = 0;
+    if (branch_rows(who, e, branches, &rows) != HG_OK) return HG_E_INVALID;
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    StepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.hmap = e->hmap;
+    a.nsteps = horizon;
+    a.retrim_slot = -1;
+    PolicyArgs pol;
+    pol.pk = e->policy_dev;
+    pol.obs0 = obs0;
+    BranchArgs br;
+    br.ret = ret;
+    br.alive_steps = alive_steps;
+    br.end_info = end_info;
+    br.branches = (uint32_t)branches;
+    br.gamma = gamma;
+    bp.residual = residual;
+    bp.bootstrap = bootstrap;
+    bp.value_scale = value_scale;
+    dispatch_rollout_branch_policy(e, (hipStream_t)stream, a, pol, br, bp, rows, noise_mode == HG_BRANCH_NOISE_OFF);
     HIP_TRY(hipGetLastError());
     return HG_OK;
 }

@@ -243,4 +243,30 @@ __device__ __forceinline__ Eval policy_eval(const Weights& w, const float* __res
     return e;
 }
 
+// The applied-action bounds of hg_policy_act_mean / hg_rollout_branch_policy, by value in the kernel
+// arguments (clamp == 0: no bounds).
+struct ActBox {
+    float lo[4], hi[4];
+    int32_t clamp;
+};
+
+// The action of a policy-guided branch: the policy's mean `mu` (policy_eval(..., sample = false).a) plus the
+// row's residual `res` -- one fp32 add per component, none at all without a residual (has_res,
+// wave-uniform) -- clamped as hg_mppi_sample clamps its candidates.  hg_policy_act_mean's kernel and the
+// branch kernel both call it.
+__device__ __forceinline__ float4 residual_action(float4 mu, float4 res, bool has_res, const ActBox& box) {
+    float v[4] = {mu.x, mu.y, mu.z, mu.w};
+    if (has_res) {
+        v[0] = v[0] + res.x;
+        v[1] = v[1] + res.y;
+        v[2] = v[2] + res.z;
+        v[3] = v[3] + res.w;
+    }
+    if (box.clamp) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[c] = fminf(fmaxf(v[c], box.lo[c]), box.hi[c]);
+    }
+    return make_float4(v[0], v[1], v[2], v[3]);
+}
+
 }  // namespace hgp

@@ -27,6 +27,7 @@ HG_AUTORESET_SAME_STEP, HG_AUTORESET_NEXT_STEP = 0, 1
 AUTORESET_MODES = {"same_step": HG_AUTORESET_SAME_STEP, "next_step": HG_AUTORESET_NEXT_STEP}
 HG_BRANCH_NOISE_ENV, HG_BRANCH_NOISE_OFF = 0, 1
 BRANCH_NOISE_MODES = {"env": HG_BRANCH_NOISE_ENV, "off": HG_BRANCH_NOISE_OFF}
+HG_BOOTSTRAP_NONE, HG_BOOTSTRAP_VALUE = 0, 1
 HG_ABI_VERSION = 3
 HG_PPO_N_PARAMS = 5641
 HG_PPO_OPT_STATE_BYTES = 45248
@@ -150,6 +151,12 @@ _SIGS = {
                                         ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.c_uint64, _P,
                                         _P]),
     "hg_mppi_update": (ctypes.c_int32, [_P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _P, _P]),
+    "hg_policy_act_mean": (ctypes.c_int32, [_P, _P, _P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                            _P, _P, _P]),
+    "hg_rollout_branch_policy": (ctypes.c_int32, [_P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+                                                  ctypes.c_int32, ctypes.POINTER(ctypes.c_float),
+                                                  ctypes.POINTER(ctypes.c_float), ctypes.c_int32, ctypes.c_float, _P, _P,
+                                                  _P, _P]),
     "hg_trim_batch": (ctypes.c_int32, [_P, _P, ctypes.c_int64, _P, _P, _P, _P, _P]),
     "hg_retrim_failures": (ctypes.c_int32, [_P, ctypes.POINTER(ctypes.c_int64)]),
     "hg_set_retrim_overlap": (ctypes.c_int32, [_P, ctypes.c_int32]),

@@ -1073,6 +1073,75 @@ class HeliVecEnv(*_VEC_BASES):
         self._check(self.lib.hg_mppi_update(self._h, _ptr(a), _ptr(g), H, B, float(lam), _ptr(o), self._stream()))
         return o
 
+    # ------------------------------------------------------------------ policy-guided planning
+    def _act_bounds(self, lo, hi):
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi go together: both given (a scalar or 4 values each) or both None")
+        if lo is None:
+            return None, None
+        return self._four(lo, "lo"), self._four(hi, "hi")
+
+    def policy_act_mean(self, obs=None, residual=None, lo=None, hi=None, out=None, value=False):
+        """The policy's MEAN action plus a residual, clamped (hg_policy_act_mean): out [N,4] =
+        clamp(mu(obs) + residual, lo, hi) for `obs` [N,17] (default: `self.obs`).  Nothing is drawn, even for
+        a stochastic policy; the env is not modified.  residual [N,4] or None; lo / hi: a scalar or 4 values
+        each, or both None for no clamp.  value=True returns (actions, V(obs) [N]) and needs a value head.
+        policy_act_mean then step(), repeated, is bitwise a branch of rollout_branch_policy()."""
+        t = self.torch
+        o = self._obs_arg(obs, "obs")
+        r = None if residual is None else self._plan_tensor(residual, (self.num_envs, _abi.HG_N_ACT), "residual")
+        l, h = self._act_bounds(lo, hi)
+        if out is None:
+            out = t.empty((self.num_envs, _abi.HG_N_ACT), dtype=t.float32, device=self.device)
+        a = self._plan_tensor(out, (self.num_envs, _abi.HG_N_ACT), "out")
+        v = t.empty((self.num_envs,), dtype=t.float32, device=self.device) if value else None
+        self._keep_plan = (o, r)
+        self._check(self.lib.hg_policy_act_mean(self._h, _ptr(o), _ptr(r), l, h, _ptr(a), _ptr(v), self._stream()))
+        return (a, v) if value else a
+
+    def rollout_branch_policy(self, residuals, branches, obs0=None, gamma=1.0, noise="env", lo=None, hi=None,
+                              bootstrap=False, value_scale=1.0, out=None, horizon=None):
+        """rollout_branch() with the env's policy inside the branches (hg_rollout_branch_policy): branch b of
+        env e starts from the env's state and `obs0[e]` (default: `self.obs`) and takes
+        a_t = clamp(mu(o_t) + residuals[t, e * branches + b], lo, hi), o_t its own latest observation.
+        residuals [H, N*branches, 4], or None with horizon=H (no residual: pure policy evaluation).  bootstrap=True:
+        a branch that survives the horizon, or is truncated without terminating, adds
+        gamma^T * value_scale * V(its last observation) (needs a value head); value_scale = 1 / reward_scale
+        turns a critic trained on scaled rewards into raw reward units.  Returns rollout_branch's dict."""
+        t = self.torch
+        B, N = self._plan_count(branches, "branches"), self.num_envs
+        if residuals is None:
+            if horizon is None:
+                raise ValueError("residuals=None needs horizon=H")
+            H, r = self._plan_count(horizon, "horizon"), None
+        else:
+            if not isinstance(residuals, t.Tensor) or residuals.ndim != 3 or residuals.shape[0] < 1:
+                raise ValueError(f"residuals must be a [H, {N * B}, 4] tensor (or None with horizon=H)")
+            H = int(residuals.shape[0])
+            if horizon is not None and int(horizon) != H:
+                raise ValueError(f"horizon {horizon!r} does not match residuals' {H} steps")
+            r = self._plan_tensor(residuals, (H, N * B, _abi.HG_N_ACT), "residuals")
+        o0 = self._obs_arg(obs0, "obs0")
+        if noise not in _abi.BRANCH_NOISE_MODES:
+            raise ValueError(f"noise must be one of {sorted(_abi.BRANCH_NOISE_MODES)}, got {noise!r}")
+        l, h = self._act_bounds(lo, hi)
+        value_scale = float(value_scale)
+        if not np.isfinite(value_scale):
+            raise ValueError(f"value_scale must be finite, got {value_scale!r}")
+        if out is None:
+            out = dict(returns=t.empty((N, B), dtype=t.float32, device=self.device),
+                       alive_steps=t.empty((N, B), dtype=t.int32, device=self.device),
+                       end_info=t.empty((N, B), dtype=t.uint8, device=self.device))
+        ret = self._plan_tensor(out["returns"], (N, B), "out['returns']")
+        alive = self._plan_tensor(out["alive_steps"], (N, B), "out['alive_steps']", t.int32)
+        end = self._plan_tensor(out["end_info"], (N, B), "out['end_info']", t.uint8)
+        self._keep_plan = (o0, r)
+        self._check(self.lib.hg_rollout_branch_policy(
+            self._h, _ptr(o0), _ptr(r), H, B, float(gamma), _abi.BRANCH_NOISE_MODES[noise], l, h,
+            _abi.HG_BOOTSTRAP_VALUE if bootstrap else _abi.HG_BOOTSTRAP_NONE, value_scale, _ptr(ret), _ptr(alive),
+            _ptr(end), self._stream()))
+        return out
+
     def trim_batch(self, wind_ned):
         """Device batched trim (hg_trim_batch) of this env's trim condition against each row of
         `wind_ned` [K,3] (ft/s NED): the reset the reference computes from its second episode on.

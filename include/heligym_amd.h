@@ -667,6 +667,57 @@ int32_t hg_mppi_sample(hg_env* env, const float* nominal_dev, int32_t horizon, i
 int32_t hg_mppi_update(hg_env* env, const float* actions_dev, const float* return_dev, int32_t horizon,
                        int32_t branches, float lambda, float* nominal_out_dev, void* stream);
 
+/* ---- Policy-guided planning: the handle's policy inside the branches, its value head behind them.
+ *
+ * A candidate is *policy + residual*: closed-loop, so the policy meets each gust and the residual only has
+ * to improve on it; and a row the horizon cuts is worth V of its last observation instead of nothing.
+ * hg_mppi_sample and hg_mppi_update work unchanged on residual sequences.  Both calls below are
+ * asynchronous on `stream`, allocate nothing, can be captured into a graph, and do not modify the env
+ * (state, counters, azimuth records, chain bookkeeping, overlapped re-trim), like the three above.
+ *
+ * hg_policy_act_mean: actions[i] = clamp(mu(obs[i]) + residual[i]) and value[i] = V(obs[i]).
+ *   mu is the policy's MEAN: the noise (log_std) is ignored even for a stochastic policy image, nothing is
+ *   drawn, no counter is read.  mu is bitwise hg_policy_act's action for the same weights packed without
+ *   log_std.  The sum is one fp32 add per component (no add at all when residual_dev is NULL); the clamp is
+ *   hg_mppi_sample's fminf(fmaxf(x, lo[c]), hi[c]); lo and hi are host arrays of 4 passed by value into the
+ *   kernel's arguments, both NULL for no clamp.  value_dev is bitwise hg_policy_eval's and needs a value
+ *   head.  The same device function as hg_rollout_branch_policy's: acting with it and stepping (hg_step) in
+ *   turn is bitwise that call's branch.
+ *   HG_E_INVALID: exactly one of lo / hi NULL, a NaN bound or lo[c] > hi[c], obs_dev NULL, residual_dev or
+ *   actions_dev not 16-byte aligned, no policy set, value_dev without a value head. */
+int32_t hg_policy_act_mean(hg_env* env, const float* obs_dev, const float* residual_dev, const float lo[4],
+                           const float hi[4], float* actions_dev, float* value_dev, void* stream);
+
+/* hg_rollout_branch_policy: hg_rollout_branch with the actions computed inside the rows.  obs0_dev [N,17]:
+ * the envs' current observations; residual_dev [horizon, N*branches, 4] (16-byte aligned) or NULL; outputs
+ * as hg_rollout_branch's.  Row r = e * branches + b.
+ *   Unchanged from hg_rollout_branch: the env's state and counters are read as its next hg_step would read
+ *   them; never a reset inside a branch; HG_RESET_RETRIM handles are accepted; the rows of an env waiting
+ *   for its next-step reset return (0, 0, 0); noise_mode, alive_steps and end_info.
+ *   Observations: o_0 = obs0[e]; o_{t+1} is the observation step t produced.
+ *   Action, while the row is alive at step t: a_t = clamp(mu(o_t) + residual[t, r]), exactly
+ *     hg_policy_act_mean's (mean, one fp32 add, clamp; lo / hi both NULL: no clamp).
+ *   Step and return: the step hg_rollout would take with a_t; G = fma(disc, reward_t, G), then
+ *     disc = disc * gamma, from G = 0, disc = 1.
+ *   bootstrap HG_BOOTSTRAP_VALUE: hg_rollout_ac's next_value rule applied to a branch.  A row that survives
+ *     the horizon, or whose ending step is truncated and not terminated, gets one more term
+ *     G = fma(disc, value_scale * V(o'), G): o' the observation its last step produced, disc the value after
+ *     that step's multiply, value_scale * V one fp32 multiply.  A terminated row gets nothing.  A critic
+ *     trained on hg_rollout_stats' scaled rewards scores in raw reward units with
+ *     value_scale = 1 / reward_scale.
+ *   One forward pass per step gives mu(o_t) and V(o_t); with the bootstrap one more pass follows the last
+ *   step.  One wave per SIMD, the weights in registers across the steps; counted by hg_debug_launches as a
+ *   lone-wave launch (out[4]), like hg_rollout_policy's.
+ *   HG_E_INVALID, nothing touched: what hg_rollout_branch refuses; no policy set; bootstrap outside the
+ *   enum; HG_BOOTSTRAP_VALUE without a value head; a non-finite value_scale; exactly one of lo / hi NULL,
+ *   a NaN bound or lo[c] > hi[c]; obs0_dev or return_dev NULL; a misaligned pointer. */
+enum { HG_BOOTSTRAP_NONE = 0, HG_BOOTSTRAP_VALUE = 1 };
+
+int32_t hg_rollout_branch_policy(hg_env* env, const float* obs0_dev, const float* residual_dev, int32_t horizon,
+                                 int32_t branches, float gamma, int32_t noise_mode, const float lo[4],
+                                 const float hi[4], int32_t bootstrap, float value_scale, float* return_dev,
+                                 int32_t* alive_steps_dev, uint8_t* end_info_dev, void* stream);
+
 /* Batched device trim:HelicopterDynamics.trim (helicopter_dynamics.py:491-576) of the env's trim
  * condition against `count` winds at once — the reset path of reset_mode HG_RESET_RETRIM, exposed
  * for direct use.  Same Newton iteration as hg_trim (fp64, trial point rounded to fp32), with the
@@ -725,7 +776,8 @@ int32_t hg_debug_queues(hg_env* env, int32_t* out);
  * hg_step_chained, hg_step_rows), out[1] steps whose launch held the previous step's re-trims
  * (hg_set_retrim_overlap), out[2] run-time specialised kernel launches, out[3] small-batch helper
  * kernel launches, out[4] lone-wave (one or two waves per SIMD) launches, out[5] bulk launches
- * (out[3..5] count hg_rollout's too, out[4..5] hg_rollout_branch's).  Host only. */
+ * (out[3..5] count hg_rollout's too, out[4..5] hg_rollout_branch's, out[4] hg_rollout_branch_policy's).
+ * Host only. */
 int32_t hg_debug_launches(const hg_env* env, int64_t* out);
 
 /* HG_RESET_RETRIM with next-step auto-reset (gymnasium's default, make_vec's): the episodes a step ends
