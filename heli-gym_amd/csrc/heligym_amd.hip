@@ -1260,6 +1260,58 @@ __global__ __launch_bounds__(64) void mppi_update_kernel(const float* __restrict
     }
 }
 
+// hg_mppi_value: what hg_mppi_update's weights make of the returns themselves, one wave per env.  The
+// weights are that kernel's (same G_max, same expression, LDS up to HG_MPPI_LDS_BRANCHES and recomputed past
+// it); every lane runs the same chains over b ascending -- num = fma(w, G, num), den = den + w, the chain
+// hg_mppi_update runs on an action column, and sq = fma(w, w, sq) -- and lane 0 stores.  A non-finite G_b has
+// weight 0 and is left out of the chain as a value too (0 * inf would poison the sum).
+__global__ __launch_bounds__(64) void mppi_value_kernel(const float* __restrict__ ret, uint32_t branches, float k,
+                                                        float* __restrict__ value, float* __restrict__ best,
+                                                        float* __restrict__ ess) {
+    __shared__ float s_w[HG_MPPI_LDS_BRANCHES];
+    const int lane = threadIdx.x;
+    const int64_t e = blockIdx.x;
+    const float* G = ret + e * branches;
+    float gmax = -INFINITY;
+    for (uint32_t b = lane; b < branches; b += 64) {
+        const float g = G[b];
+        gmax = isfinite(g) ? fmaxf(gmax, g) : gmax;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) gmax = fmaxf(gmax, __shfl_xor(gmax, o));
+    const bool none = !(gmax > -INFINITY);   // (uniform) no finite return
+    auto weight = [&](uint32_t b) {
+        const float g = G[b];
+        return isfinite(g) ? exp2f((g - gmax) * k) : 0.f;
+    };
+    const bool in_lds = branches <= HG_MPPI_LDS_BRANCHES;   // (uniform)
+    if (in_lds && !none) {
+        for (uint32_t b = lane; b < branches; b += 64) s_w[b] = weight(b);
+    }
+    __syncthreads();
+    float num = 0.f, den = 0.f, sq = 0.f;
+    if (!none) {
+#pragma unroll 4
+        for (uint32_t b = 0; b < branches; ++b) {
+            const float w = in_lds ? s_w[b] : weight(b);
+            const float g = G[b];
+            num = fmaf(w, isfinite(g) ? g : 0.f, num);
+            den = den + w;
+            sq = fmaf(w, w, sq);
+        }
+    }
+    // (the quotients are formed unconditionally: under a select the compiler speculates the division and
+    // drops the accuracy it was given, and the value would no longer be hg_mppi_update's quotient)
+    const float mean = num / den;
+    const float dd = den * den;
+    const float n_eff = dd / sq;
+    if (lane == 0) {
+        value[e] = none ? 0.f : mean;
+        if (best) best[e] = gmax;
+        if (ess) ess[e] = none ? 0.f : n_eff;
+    }
+}
+
 // reset_mode RETRIM with next-step auto-reset (hg_env::ov): one launch holds the trims of the previous
 // step's ends -- its first `tb` blocks, one wave per trim (retrim_body.h) -- and this step, whose
 // deferred resets store only their step counter while those trims write the rest.  Both parts fit
@@ -3332,6 +3384,45 @@ int32_t hg_ppo_adam(hg_env* e, float* theta, const float* grad, const float* sta
     return HG_OK;
 }
 
+// hg_ppo_update's and hg_bc_update's loop, after their checks: clear `stop`; per epoch a permutation keyed on the
+// state's `seen` word; per minibatch grad_call(index slice, rows, stats row) then the optimiser step.
+}  // extern "C" (a template has C++ linkage; the block reopens below it)
+
+template <typename GradCall>
+static int32_t update_loop(const char* who, hg_env* e, float* theta, const float* grad, int64_t B, int32_t n_epochs,
+                           int32_t n_minibatches, uint64_t seed, int32_t* index, float* stats_out, void* state,
+                           const hg_ppo_opt_cfg* cfg, void* stream, GradCall grad_call) {
+    if (n_epochs < 1) return fail(HG_E_INVALID, std::string(who) + ": n_epochs must be >= 1");
+    if (n_minibatches < 1 || (int64_t)n_minibatches > B)
+        return fail(HG_E_INVALID, std::string(who) + ": n_minibatches must be in 1 .. B");
+    if (cfg->target_kl > 0.f && !stats_out)
+        return fail(HG_E_INVALID,
+                    std::string(who) + ": target_kl needs stats_out (the early stop reads each minibatch's row)");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    hipStream_t s = (hipStream_t)stream;
+    int32_t* const tail = (int32_t*)state + hgk::kOptTail;
+    // (a kernel, not a 4-byte memset: replayed memset nodes have left such words stale, DESIGN section 3)
+    hipLaunchKernelGGL(zero_counts_kernel, dim3(1), dim3(64), 0, s, tail + hgk::kOptStop, (int32_t*)nullptr,
+                       (int32_t*)nullptr, (int32_t*)nullptr);
+    HIP_TRY(hipGetLastError());
+    for (int32_t ep = 0; ep < n_epochs; ++ep) {
+        int32_t rc = hg_ppo_shuffle(e, B, seed, 0, tail + hgk::kOptSeen, index, stream);
+        if (rc != HG_OK) return rc;
+        for (int32_t j = 0; j < n_minibatches; ++j) {
+            // floor(j B / n): B < 2^31 and n <= B, so the product fits 64 bits
+            const int64_t lo = (int64_t)j * B / n_minibatches, hi = (int64_t)(j + 1) * B / n_minibatches;
+            float* const row = stats_out ? stats_out + 8 * ((int64_t)ep * n_minibatches + j) : nullptr;
+            rc = grad_call(index + lo, hi - lo, row);
+            if (rc != HG_OK) return rc;
+            HIP_TRY(ppo_adam_launch(theta, grad, row, state, cfg, s));
+        }
+    }
+    return HG_OK;
+}
+
+extern "C" {
+
 int32_t hg_ppo_update(hg_env* e, float* theta, const float* obs_mean, const float* obs_scale, const float* obs,
                       const float* actions, const float* logp_old, const float* adv, const float* ret, int64_t B, float clip,
                       float vf_coef, float ent_coef, float* grad, void* workspace, int32_t n_epochs, int32_t n_minibatches,
@@ -3343,33 +3434,89 @@ int32_t hg_ppo_update(hg_env* e, float* theta, const float* obs_mean, const floa
                             ent_coef, grad, stats_out, workspace);
     if (rc == HG_OK) rc = ppo_adam_check(e, theta, grad, stats_out, state, cfg);
     if (rc != HG_OK) return rc;
-    if (n_epochs < 1) return fail(HG_E_INVALID, "hg_ppo_update: n_epochs must be >= 1");
-    if (n_minibatches < 1 || (int64_t)n_minibatches > B)
-        return fail(HG_E_INVALID, "hg_ppo_update: n_minibatches must be in 1 .. B");
-    if (cfg->target_kl > 0.f && !stats_out)
-        return fail(HG_E_INVALID, "hg_ppo_update: target_kl needs stats_out (the early stop reads each minibatch's row)");
+    return update_loop("hg_ppo_update", e, theta, grad, B, n_epochs, n_minibatches, seed, index, stats_out, state, cfg, stream,
+                       [&](const int32_t* ix, int64_t m, float* row) {
+                           return hg_ppo_grad(e, theta, obs_mean, obs_scale, obs, actions, logp_old, adv, ret, B, ix, m, clip,
+                                              vf_coef, ent_coef, grad, row, workspace, stream);
+                       });
+}
+
+// ---- the imitation loss: hg_ppo_grad's kernel with a second head (ppo_grad.hip), and hg_ppo_update's loop around it
+static int32_t bc_grad_check(const hg_env* e, const float* theta, const float* obs_mean, const float* obs_scale,
+                             const float* obs, const float* target, const float* weight, const float* value_target,
+                             int64_t B, const int32_t* index, int64_t M, int32_t mode, float vf_coef, float ent_coef,
+                             const float* grad, const float* stats, const void* workspace) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!theta || !obs || !target || !grad || !workspace)
+        return fail(HG_E_INVALID, "hg_bc_grad: theta/obs/target/grad/workspace must be device pointers");
+    if (((uintptr_t)target & 15) || ((uintptr_t)workspace & 15))
+        return fail(HG_E_INVALID, "hg_bc_grad: target and workspace must be 16-byte aligned");
+    if ((((uintptr_t)theta | (uintptr_t)obs_mean | (uintptr_t)obs_scale | (uintptr_t)obs | (uintptr_t)weight |
+          (uintptr_t)value_target | (uintptr_t)index | (uintptr_t)grad | (uintptr_t)stats) & 3) != 0)
+        return fail(HG_E_INVALID, "hg_bc_grad: every pointer must be 4-byte aligned");
+    if (B < 1) return fail(HG_E_INVALID, "hg_bc_grad: B must be >= 1");
+    if (M < 1) return fail(HG_E_INVALID, "hg_bc_grad: M must be >= 1");
+    if (M > (int64_t)INT32_MAX - 255) return fail(HG_E_INVALID, "hg_bc_grad: M must be at most 2^31 - 256");
+    if (!index && M != B) return fail(HG_E_INVALID, "hg_bc_grad: without an index M must equal B");
+    if (mode != HG_BC_NLL && mode != HG_BC_MSE) return fail(HG_E_INVALID, "hg_bc_grad: mode must be HG_BC_NLL or HG_BC_MSE");
+    if (!std::isfinite(vf_coef) || vf_coef < 0.f || !std::isfinite(ent_coef) || ent_coef < 0.f)
+        return fail(HG_E_INVALID, "hg_bc_grad: vf_coef and ent_coef must be finite and >= 0");
+    if (!value_target && vf_coef != 0.f)
+        return fail(HG_E_INVALID, "hg_bc_grad: value_target is NULL, so vf_coef must be 0");
+    return HG_OK;
+}
+
+int32_t hg_bc_grad(hg_env* e, const float* theta, const float* obs_mean, const float* obs_scale, const float* obs,
+                   const float* target, const float* weight, const float* value_target, int64_t B, const int32_t* index,
+                   int64_t M, int32_t mode, float vf_coef, float ent_coef, float* grad, float* stats, void* workspace,
+                   void* stream) {
+    const int32_t rc = bc_grad_check(e, theta, obs_mean, obs_scale, obs, target, weight, value_target, B, index, M, mode,
+                                     vf_coef, ent_coef, grad, stats, workspace);
+    if (rc != HG_OK) return rc;
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
-    hipStream_t s = (hipStream_t)stream;
-    int32_t* const tail = (int32_t*)state + hgk::kOptTail;
-    // (a kernel, not a 4-byte memset: replayed memset nodes have left such words stale, DESIGN section 3)
-    hipLaunchKernelGGL(zero_counts_kernel, dim3(1), dim3(64), 0, s, tail + hgk::kOptStop, (int32_t*)nullptr,
-                       (int32_t*)nullptr, (int32_t*)nullptr);
-    HIP_TRY(hipGetLastError());
-    for (int32_t ep = 0; ep < n_epochs; ++ep) {
-        rc = hg_ppo_shuffle(e, B, seed, 0, tail + hgk::kOptSeen, index, stream);
-        if (rc != HG_OK) return rc;
-        for (int32_t j = 0; j < n_minibatches; ++j) {
-            // floor(j B / n): B < 2^31 and n <= B, so the product fits 64 bits
-            const int64_t lo = (int64_t)j * B / n_minibatches, hi = (int64_t)(j + 1) * B / n_minibatches;
-            float* const row = stats_out ? stats_out + 8 * ((int64_t)ep * n_minibatches + j) : nullptr;
-            rc = hg_ppo_grad(e, theta, obs_mean, obs_scale, obs, actions, logp_old, adv, ret, B, index + lo, hi - lo, clip,
-                             vf_coef, ent_coef, grad, row, workspace, stream);
-            if (rc != HG_OK) return rc;
-            HIP_TRY(ppo_adam_launch(theta, grad, row, state, cfg, s));
-        }
-    }
+    hgk::PpoGradArgs a;
+    a.theta = theta;
+    a.mean = obs_mean;
+    a.scale = obs_scale;
+    a.obs = obs;
+    a.act = target;
+    a.logp_old = nullptr;
+    a.adv = weight;
+    a.ret = value_target;
+    a.index = index;
+    a.B = B;
+    a.M = M;
+    a.clip = 0.f;
+    a.vf_coef = vf_coef;
+    a.ent_coef = ent_coef;
+    a.inv_m = 1.0f / (float)M;
+    a.grad = grad;
+    a.stats = stats;
+    a.ws = (float*)workspace;
+    HIP_TRY(hgk::launch_bc_grad(a, mode, (hipStream_t)stream));
     return HG_OK;
+}
+
+int32_t hg_bc_update(hg_env* e, float* theta, const float* obs_mean, const float* obs_scale, const float* obs,
+                     const float* target, const float* weight, const float* value_target, int64_t B, int32_t mode,
+                     float vf_coef, float ent_coef, float* grad, void* workspace, int32_t n_epochs, int32_t n_minibatches,
+                     uint64_t seed, int32_t* index, float* stats_out, void* state, const hg_ppo_opt_cfg* cfg, void* stream) {
+    int32_t rc = ppo_shuffle_check(e, B, nullptr, index);
+    if (rc == HG_OK)
+        rc = bc_grad_check(e, theta, obs_mean, obs_scale, obs, target, weight, value_target, B, index, 1, mode, vf_coef,
+                           ent_coef, grad, stats_out, workspace);
+    if (rc == HG_OK) rc = ppo_adam_check(e, theta, grad, stats_out, state, cfg);
+    if (rc != HG_OK) return rc;
+    if (cfg->target_kl > 0.f)
+        return fail(HG_E_INVALID, "hg_bc_update: target_kl must be off (<= 0): the statistics' entry 2 is no KL here");
+    hg_ppo_opt_cfg opt = *cfg;
+    opt.target_kl = 0.f;   // the optimiser's early stop reads stats[2]: off
+    return update_loop("hg_bc_update", e, theta, grad, B, n_epochs, n_minibatches, seed, index, stats_out, state, &opt, stream,
+                       [&](const int32_t* ix, int64_t m, float* row) {
+                           return hg_bc_grad(e, theta, obs_mean, obs_scale, obs, target, weight, value_target, B, ix, m, mode,
+                                             vf_coef, ent_coef, grad, row, workspace, stream);
+                       });
 }
 
 int32_t hg_set_policy_theta(hg_env* e, const float* theta, const float* obs_mean, const float* obs_scale, void* stream) {
@@ -3641,6 +3788,26 @@ int32_t hg_mppi_update(hg_env* e, const float* actions, const float* ret, int32_
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     hipLaunchKernelGGL(mppi_update_kernel, dim3((unsigned)e->n), dim3(64), 0, (hipStream_t)stream, actions, ret,
                        (int64_t)e->n, (uint32_t)branches, horizon, k, nominal_out);
+    HIP_TRY(hipGetLastError());
+    return HG_OK;
+}
+
+int32_t hg_mppi_value(hg_env* e, const float* ret, int32_t branches, float lambda, float* value, float* best, float* ess,
+                      void* stream) {
+    if (branch_shape("hg_mppi_value", 1, branches) != HG_OK) return HG_E_INVALID;
+    const float k = (float)(1.4426950408889634 / (double)lambda);   // log2(e) / lambda
+    if (!std::isfinite(lambda) || !(lambda > 0.f) || !std::isfinite(k))
+        return fail(HG_E_INVALID, "hg_mppi_value: lambda must be > 0 (and log2(e) / lambda finite in fp32)");
+    if (!ret || !value) return fail(HG_E_INVALID, "hg_mppi_value: return/value must be device pointers");
+    if ((((uintptr_t)ret | (uintptr_t)value | (uintptr_t)best | (uintptr_t)ess) & 3) != 0)
+        return fail(HG_E_INVALID, "hg_mppi_value: return, value, best and ess must be 4-byte aligned");
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    int64_t rows = 0;
+    if (branch_rows("hg_mppi_value", e, branches, &rows) != HG_OK) return HG_E_INVALID;
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    hipLaunchKernelGGL(mppi_value_kernel, dim3((unsigned)e->n), dim3(64), 0, (hipStream_t)stream, ret, (uint32_t)branches, k,
+                       value, best, ess);
     HIP_TRY(hipGetLastError());
     return HG_OK;
 }

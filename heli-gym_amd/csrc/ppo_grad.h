@@ -34,4 +34,9 @@ struct PpoGradArgs {
 // The gradient kernel, then the fixed-order reduction of its per-block partials, both on `stream`.
 hipError_t launch_ppo_grad(const PpoGradArgs& a, hipStream_t stream);
 
+// The same kernel body with the weighted imitation loss's head (hg_bc_grad), then the same reduction.
+// `a` as above with adv = the weights or nullptr (1), ret = the value targets or nullptr (no value term;
+// vf_coef is 0 then), logp_old and clip unused; mode HG_BC_NLL or HG_BC_MSE.
+hipError_t launch_bc_grad(const PpoGradArgs& a, int mode, hipStream_t stream);
+
 }  // namespace hgk

@@ -28,6 +28,8 @@
 // End of block: the four waves' sums are added in wave order through LDS and written as the block's
 // partial to the workspace; ppo_reduce_kernel adds the partials in a fixed order.  No atomics: the launch
 // shape is a function of M, so the bits are too.
+// The weighted imitation loss (hg_bc_grad) is a second head on the same body: grad_body<LOSS> below holds
+// everything, ppo_grad_kernel and bc_grad_kernel are its two instantiations.
 #include "ppo_grad.h"
 
 namespace hgk {
@@ -114,7 +116,18 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-__global__ __launch_bounds__(kThreads) void ppo_grad_kernel(const PpoGradArgs a, const int64_t tiles) {
+// The loss heads.  Everything but the head -- the forward pass, the back-propagation, the parameter sums and
+// the block's partial -- is the same code for each; the head forms d3[0..4], the log_std sums and the six
+// statistic sums of its loss from the sample's mean, value and labels.
+//   kLossPpo: the clipped surrogate (hg_ppo_grad).
+//   kLossBc:  the weighted imitation loss (hg_bc_grad); `mode` (HG_BC_NLL / HG_BC_MSE, wave-uniform) selects
+//             between the two regressions inside the head.  The argument struct's adv slot carries the
+//             weights (or nullptr: 1), ret the value targets (or nullptr: no value term), logp_old nothing.
+constexpr int kLossPpo = 0, kLossBc = 1;
+constexpr int kBcNll = 0, kBcMse = 1;   // include/heligym_amd.h's HG_BC_NLL, HG_BC_MSE
+
+template <int LOSS>
+__device__ __forceinline__ void grad_body(const PpoGradArgs& a, const int64_t tiles, const int mode) {
     __shared__ __attribute__((aligned(16))) float s_img[kSlots * 64];
     __shared__ __attribute__((aligned(16))) float s_wave[kWaves][kWaveFloats];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 31, h = lane >> 5;
@@ -190,7 +203,15 @@ __global__ __launch_bounds__(kThreads) void ppo_grad_kernel(const PpoGradArgs a,
         }
         const float4 av = *reinterpret_cast<const float4*>(a.act + row * 4);
         const float act[4] = {av.x, av.y, av.z, av.w};
-        const float lp_old = a.logp_old[row], adv = a.adv[row], ret = a.ret[row];
+        float lp_old = 0.0f, adv = 1.0f, ret = 0.0f;   // (kLossBc: adv is the weight, ret the value target)
+        if constexpr (LOSS == kLossPpo) {
+            lp_old = a.logp_old[row];
+            adv = a.adv[row];
+            ret = a.ret[row];
+        } else {
+            if (a.adv) adv = a.adv[row];
+            if (a.ret) ret = a.ret[row];
+        }
 #pragma unroll
         for (int c = 0; c < 18; ++c) RX[c * kXS + lane] = x[c];
 
@@ -246,7 +267,7 @@ __global__ __launch_bounds__(kThreads) void ppo_grad_kernel(const PpoGradArgs a,
 
         // ---- the loss's derivative with respect to this sample's mean, value and log_std
         float d3[6];
-        {
+        if constexpr (LOSS == kLossPpo) {
             float z[4], q = 0.0f;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
@@ -285,6 +306,47 @@ __global__ __launch_bounds__(kThreads) void ppo_grad_kernel(const PpoGradArgs a,
             st[2] = st[2] + (active ? -dl : 0.0f);
             st[3] = st[3] + ((active && (ratio < clip_lo || ratio > clip_hi)) ? 1.0f : 0.0f);
             st[4] = st[4] + (active ? ratio : 0.0f);
+            st[5] = st[5] + (skipped ? 1.0f : 0.0f);
+        } else {
+            // the imitation head: st = {w l, 1/2 (v - y)^2, sum (a* - mu)^2, w, logp(a*), skipped}
+            const bool nll = mode == kBcNll;   // (uniform)
+            float diff[4], z[4], q = 0.0f, sq = 0.0f;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float mu = h ? o3[1][c] : o3[0][c];
+                diff[c] = act[c] - mu;
+                z[c] = diff[c] * inv_std[c];
+                q = fmaf(z[c], z[c], q);
+                sq = fmaf(diff[c], diff[c], sq);
+            }
+            const float v = h ? o3[1][4] : o3[0][4];
+            const float logp = fmaf(-0.5f, q, -ls_sum) - 3.67575413281869070f;   // 2 ln 2 pi
+            const float w = adv;
+            const float wm = active ? w * a.inv_m : 0.0f;
+            const float g = -wm;   // NLL: dL / dlogp
+            const float verr = a.ret ? v - ret : 0.0f;
+            const float vg = a.vf_coef * verr;
+            const float gv = active ? vg * a.inv_m : 0.0f;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float gz = g * z[c];
+                const float nd = -diff[c];
+                d3[c] = nll ? gz * inv_std[c] : nd * wm;
+                sb3[c] = sb3[c] + d3[c];
+                const float zz = fmaf(z[c], z[c], -1.0f);
+                sls[c] = nll ? fmaf(g, zz, sls[c]) : sls[c];
+            }
+            d3[4] = gv;
+            d3[5] = 0.0f;
+            sb3[4] = sb3[4] + gv;
+            const float hv = 0.5f * verr;
+            const float hq = 0.5f * sq;
+            const float l = nll ? -logp : hq;
+            st[0] = st[0] + (active ? w * l : 0.0f);
+            st[1] = st[1] + (active ? hv * verr : 0.0f);
+            st[2] = st[2] + (active ? sq : 0.0f);
+            st[3] = st[3] + (active ? w : 0.0f);
+            st[4] = st[4] + (active ? logp : 0.0f);
             st[5] = st[5] + (skipped ? 1.0f : 0.0f);
         }
 #pragma unroll
@@ -462,6 +524,14 @@ __global__ __launch_bounds__(kThreads) void ppo_grad_kernel(const PpoGradArgs a,
     for (int e = tid; e < kPpoPartialFloats; e += kThreads) dst[e] = sum[e];
 }
 
+__global__ __launch_bounds__(kThreads) void ppo_grad_kernel(const PpoGradArgs a, const int64_t tiles) {
+    grad_body<kLossPpo>(a, tiles, 0);
+}
+
+__global__ __launch_bounds__(kThreads) void bc_grad_kernel(const PpoGradArgs a, const int64_t tiles, const int mode) {
+    grad_body<kLossBc>(a, tiles, mode);
+}
+
 // grad[p] = the partials' sum: chain c = 0 .. 3 adds the blocks b = c, c + 4, .. in ascending order (one
 // thread per parameter and chain, 64 parameters per block, the loads sixteen deep), then
 // ((chain 0 + chain 1) + (chain 2 + chain 3)); the entropy term's constant -ent_coef on log_std.  The
@@ -519,16 +589,30 @@ __global__ __launch_bounds__(256) void ppo_reduce_kernel(const float* __restrict
 
 }  // namespace
 
-hipError_t launch_ppo_grad(const PpoGradArgs& a, hipStream_t stream) {
+// the gradient kernel `launch` enqueues, then the reduction: the grid is a function of M alone
+template <typename Launch>
+static hipError_t launch_grad(const PpoGradArgs& a, hipStream_t stream, Launch launch) {
     const int64_t tiles = (a.M + 63) / 64;
     const int64_t want = (tiles + kWaves - 1) / kWaves;
     const int nb = (int)(want < kPpoMaxBlocks ? want : kPpoMaxBlocks);
-    hipLaunchKernelGGL(ppo_grad_kernel, dim3(nb), dim3(kThreads), 0, stream, a, tiles);
+    launch(nb, tiles);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
     hipLaunchKernelGGL(ppo_reduce_kernel, dim3((kRedItems + kRedParams - 1) / kRedParams), dim3(256), 0, stream, (const float*)a.ws, nb,
                        a.theta, a.vf_coef, a.ent_coef, a.inv_m, a.grad, a.stats);
     return hipGetLastError();
+}
+
+hipError_t launch_ppo_grad(const PpoGradArgs& a, hipStream_t stream) {
+    return launch_grad(a, stream, [&](int nb, int64_t tiles) {
+        hipLaunchKernelGGL(ppo_grad_kernel, dim3(nb), dim3(kThreads), 0, stream, a, tiles);
+    });
+}
+
+hipError_t launch_bc_grad(const PpoGradArgs& a, int mode, hipStream_t stream) {
+    return launch_grad(a, stream, [&](int nb, int64_t tiles) {
+        hipLaunchKernelGGL(bc_grad_kernel, dim3(nb), dim3(kThreads), 0, stream, a, tiles, mode);
+    });
 }
 
 }  // namespace hgk

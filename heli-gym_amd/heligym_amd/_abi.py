@@ -28,6 +28,8 @@ AUTORESET_MODES = {"same_step": HG_AUTORESET_SAME_STEP, "next_step": HG_AUTORESE
 HG_BRANCH_NOISE_ENV, HG_BRANCH_NOISE_OFF = 0, 1
 BRANCH_NOISE_MODES = {"env": HG_BRANCH_NOISE_ENV, "off": HG_BRANCH_NOISE_OFF}
 HG_BOOTSTRAP_NONE, HG_BOOTSTRAP_VALUE = 0, 1
+HG_BC_NLL, HG_BC_MSE = 0, 1
+BC_MODES = {"nll": HG_BC_NLL, "mse": HG_BC_MSE}
 HG_ABI_VERSION = 3
 HG_PPO_N_PARAMS = 5641
 HG_PPO_OPT_STATE_BYTES = 45248
@@ -140,6 +142,11 @@ _SIGS = {
     "hg_ppo_update": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int64, ctypes.c_float, ctypes.c_float,
                                        ctypes.c_float, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, _P, _P, _P,
                                        ctypes.POINTER(hg_ppo_opt_cfg), _P]),
+    "hg_bc_grad": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int32,
+                                    ctypes.c_float, ctypes.c_float, _P, _P, _P, _P]),
+    "hg_bc_update": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_float,
+                                      ctypes.c_float, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, _P, _P, _P,
+                                      ctypes.POINTER(hg_ppo_opt_cfg), _P]),
     "hg_set_policy_theta": (ctypes.c_int32, [_P, _P, _P, _P, _P]),
     "hg_rollout_stats_state_bytes": (ctypes.c_int64, [ctypes.c_int64]),
     "hg_rollout_stats_init": (ctypes.c_int32, [_P, _P, _P]),
@@ -151,6 +158,7 @@ _SIGS = {
                                         ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.c_uint64, _P,
                                         _P]),
     "hg_mppi_update": (ctypes.c_int32, [_P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _P, _P]),
+    "hg_mppi_value": (ctypes.c_int32, [_P, _P, ctypes.c_int32, ctypes.c_float, _P, _P, _P, _P]),
     "hg_policy_act_mean": (ctypes.c_int32, [_P, _P, _P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                             _P, _P, _P]),
     "hg_rollout_branch_policy": (ctypes.c_int32, [_P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,

@@ -69,6 +69,15 @@ class MPPI:
         self._iterate(iterations)
         return self.nominal[0]
 
+    def value(self, out=None):
+        """What the planner thinks each env's state is worth (hg_mppi_value of the last scored candidate set,
+        with the planner's own temperature): a dict of value [N] (the softmax-weighted mean return: with
+        PolicyMPPI's bootstrap the n-step lookahead value, a critic's regression target), best [N] (the largest
+        finite return) and ess [N] (the weights' effective sample size).  `out`: such a dict to reuse."""
+        if self.scores is None:
+            raise ValueError("value() needs a scored candidate set: call plan() first")
+        return self.env.mppi_value(self.scores["returns"], self.branches, self.lam, out=out)
+
     def shift(self):
         """Advance the nominal by one step: row t takes row t + 1, the last row is repeated."""
         if self.horizon > 1:

@@ -244,3 +244,48 @@ def ppo_loss(theta_or_params, obs, actions, logp_old, adv, ret, clip, vf_coef, e
         stats = torch.stack([pol.mean(), val.mean(), (logp_old - logp).mean(), out, H.detach(), L.detach(), r.mean(),
                              torch.zeros((), dtype=theta.dtype, device=theta.device)])
     return L, stats
+
+
+BC_MODES = ("nll", "mse")
+
+
+def bc_loss(theta_or_params, obs, target, weight, value_target, mode, vf_coef, ent_coef, obs_mean=None, obs_scale=None):
+    """The weighted imitation loss hg_bc_grad differentiates (include/heligym_amd.h), in plain torch and in the
+    dtype of `theta` (an ActorCriticParams, or a flat [5641] tensor in PPO_LAYOUT's order, which may require
+    grad): the counterpart of ppo_loss.  obs [M,17], target [M,4]: the minibatch's rows and the actions to
+    regress onto; weight [M] or None (1); value_target [M] or None (no value term: vf_coef must be 0).
+    mode "nll": l = -logp(target) under the policy's Gaussian; "mse": l = 1/2 sum_c (target - mu)^2.
+        L = mean(w l + vf_coef * 1/2 (v - y)^2) - ent_coef * H
+    Returns (L, stats) with stats the eight values of hg_bc_grad's stats: mean w l, mean 1/2 (v - y)^2, mean
+    squared action error, mean w, H, L, mean logp(target), 0 (the skipped entries)."""
+    import torch
+    if mode not in BC_MODES:
+        raise ValueError(f"bc_loss: mode must be one of {BC_MODES}, got {mode!r}")
+    if value_target is None and vf_coef != 0:
+        raise ValueError("bc_loss: value_target is None, so vf_coef must be 0")
+    theta = theta_or_params.theta if isinstance(theta_or_params, ActorCriticParams) else theta_or_params
+    p = ppo_views(theta)
+    x = obs
+    if obs_mean is not None:
+        x = x - obs_mean
+    if obs_scale is not None:
+        x = x * obs_scale
+    h1 = torch.tanh(x @ p["W1"].T + p["b1"])
+    h2 = torch.tanh(h1 @ p["W2"].T + p["b2"])
+    mu = h2 @ p["W3"].T + p["b3"]
+    v = h2 @ p["w_v"] + p["b_v"]
+    ls = p["log_std"]
+    diff = target - mu
+    z = diff * torch.exp(-ls)
+    logp = -0.5 * (z * z).sum(-1) - ls.sum() - 2.0 * LOG_2PI
+    sq = (diff * diff).sum(-1)
+    l = -logp if mode == "nll" else 0.5 * sq
+    wl = l if weight is None else weight * l
+    val = torch.zeros_like(wl) if value_target is None else 0.5 * (v - value_target) ** 2
+    H = ls.sum() + 2.0 * (1.0 + LOG_2PI)
+    L = (wl + vf_coef * val).mean() - ent_coef * H
+    with torch.no_grad():
+        one = torch.ones((), dtype=theta.dtype, device=theta.device)
+        stats = torch.stack([wl.mean(), val.mean(), sq.mean(), one if weight is None else weight.mean() * one,
+                             H.detach(), L.detach(), logp.mean(), 0.0 * one])
+    return L, stats

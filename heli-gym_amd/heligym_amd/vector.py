@@ -710,6 +710,14 @@ class HeliVecEnv(*_VEC_BASES):
                              f"got {got}")
         return x
 
+    def _workspace(self):
+        """hg_ppo_grad's workspace for the per-block partial sums, allocated once per env."""
+        ws = getattr(self, "_ppo_workspace", None)
+        if ws is None:
+            ws = self._ppo_workspace = self.torch.empty((int(self.lib.hg_ppo_grad_workspace_bytes()),),
+                                                        dtype=self.torch.uint8, device=self.device)
+        return ws
+
     def ppo_grad(self, params, obs, actions, logp_old, adv, ret, index=None, clip=0.2, vf_coef=1.0, ent_coef=0.0,
                  obs_mean=None, obs_scale=None, stats=None):
         """The clipped PPO loss's gradient over a minibatch in one kernel (hg_ppo_grad; the loss is
@@ -747,10 +755,7 @@ class HeliVecEnv(*_VEC_BASES):
         if stats is None:
             stats = t.empty((8,), dtype=t.float32, device=self.device)
         st = self._ppo_tensor(stats, (8,), "stats")
-        ws = getattr(self, "_ppo_workspace", None)
-        if ws is None:
-            ws = self._ppo_workspace = t.empty((int(self.lib.hg_ppo_grad_workspace_bytes()),), dtype=t.uint8,
-                                               device=self.device)
+        ws = self._workspace()
         self._keep_ppo = (theta, o, a, lp, ad, rt, ix, mean, scale)
         self._check(self.lib.hg_ppo_grad(self._h, _ptr(theta), _ptr(mean), _ptr(scale), _ptr(o), _ptr(a), _ptr(lp),
                                          _ptr(ad), _ptr(rt), B, _ptr(ix), M, float(clip), float(vf_coef),
@@ -891,15 +896,112 @@ class HeliVecEnv(*_VEC_BASES):
             if index is None or tuple(index.shape) != (B,):
                 index = self._ppo_update_index = t.empty((B,), dtype=t.int32, device=self.device)
         ix = self._opt_tensor(index, (B,), "index", t.int32)
-        ws = getattr(self, "_ppo_workspace", None)
-        if ws is None:
-            ws = self._ppo_workspace = t.empty((int(self.lib.hg_ppo_grad_workspace_bytes()),), dtype=t.uint8,
-                                               device=self.device)
+        ws = self._workspace()
         self._keep_ppo_update = (theta, grad, s, o, a, lp, ad, rt, mean, scale, st, ix, lr_dev)
         self._check(self.lib.hg_ppo_update(self._h, _ptr(theta), _ptr(mean), _ptr(scale), _ptr(o), _ptr(a), _ptr(lp),
                                            _ptr(ad), _ptr(rt), B, float(clip), float(vf_coef), float(ent_coef), _ptr(grad),
                                            _ptr(ws), epochs, minibatches, int(seed) & (2 ** 64 - 1), _ptr(ix), _ptr(st),
                                            _ptr(s), ctypes.byref(cfg), self._stream()))
+        if publish:
+            self.set_policy_theta(params, mean, scale)
+        return st
+
+    # ------------------------------------------------------------------ the imitation loss: gradient and update
+    def _bc_rows(self, who, obs, target, weight, value_target, mode, vf_coef, ent_coef, obs_mean, obs_scale):
+        """The checked row tensors and scalars bc_grad and bc_update share (ValueError for what needs no device)."""
+        import math
+        t = self.torch
+        if mode not in _abi.BC_MODES:
+            raise ValueError(f"{who}: mode must be one of {sorted(_abi.BC_MODES)}, got {mode!r}")
+        vf_coef, ent_coef = float(vf_coef), float(ent_coef)
+        if not (math.isfinite(vf_coef) and vf_coef >= 0 and math.isfinite(ent_coef) and ent_coef >= 0):
+            raise ValueError(f"{who}: vf_coef and ent_coef must be finite and >= 0, got {vf_coef}, {ent_coef}")
+        if value_target is None and vf_coef != 0:
+            raise ValueError(f"{who}: value_target is None, so vf_coef must be 0, got {vf_coef}")
+        if not isinstance(obs, t.Tensor) or obs.ndim < 2 or obs.shape[-1] != _abi.HG_N_OBS:
+            raise ValueError(f"{who}: obs must be a [..., 17] tensor")
+        B = int(obs.numel() // _abi.HG_N_OBS)
+        if B < 1 or B > 2 ** 31 - 256:
+            raise ValueError(f"{who}: obs must have 1 .. 2^31 - 256 rows, got {B}")
+        lead = tuple(obs.shape[:-1])
+        o = self._opt_tensor(obs, lead + (_abi.HG_N_OBS,), "obs", who=who)
+        a = self._opt_tensor(target, lead + (_abi.HG_N_ACT,), "target", who=who)
+        w = None if weight is None else self._opt_tensor(weight, lead, "weight", who=who)
+        y = None if value_target is None else self._opt_tensor(value_target, lead, "value_target", who=who)
+        mean = None if obs_mean is None else self._opt_tensor(obs_mean, (_abi.HG_N_OBS,), "obs_mean", who=who)
+        scale = None if obs_scale is None else self._opt_tensor(obs_scale, (_abi.HG_N_OBS,), "obs_scale", who=who)
+        return B, o, a, w, y, mean, scale, _abi.BC_MODES[mode], vf_coef, ent_coef
+
+    def bc_grad(self, params, obs, target, weight=None, value_target=None, index=None, mode="nll", vf_coef=0.0,
+                ent_coef=0.0, obs_mean=None, obs_scale=None, stats=None):
+        """The weighted imitation loss's gradient over a minibatch in one kernel (hg_bc_grad; the loss is
+        heligym_amd.policy.bc_loss): a regression of the policy's Gaussian onto `target` [B,4] at `obs` [B,17]
+        plus a value regression onto `value_target` [B].  mode "nll": -logp(target), log_std is trained;
+        "mse": 1/2 |target - mean|^2.  weight [B] or None (1) multiplies each row's action term;
+        value_target None needs vf_coef == 0.  params, index, obs_mean / obs_scale, stats: as ppo_grad's.
+        Returns (params.grad, stats [8]: weighted action term, value term, mean squared action error, mean
+        weight, entropy, loss, mean logp(target), skipped entries).  Asynchronous on the current stream,
+        allocates nothing after the first call, capturable; the env is not modified."""
+        t = self.torch
+        who = "bc_grad"
+        theta = self._opt_tensor(getattr(params, "theta", None), (_abi.HG_PPO_N_PARAMS,), "params.theta", who=who)
+        grad = self._opt_tensor(getattr(params, "grad", None), (_abi.HG_PPO_N_PARAMS,), "params.grad", who=who)
+        B, o, a, w, y, mean, scale, m, vf_coef, ent_coef = self._bc_rows(who, obs, target, weight, value_target, mode,
+                                                                         vf_coef, ent_coef, obs_mean, obs_scale)
+        M, ix = B, None
+        if index is not None:
+            if not isinstance(index, t.Tensor) or index.ndim != 1 or index.shape[0] < 1:
+                raise ValueError("bc_grad: index must be a non-empty int32 [M] tensor")
+            M = int(index.shape[0])
+            ix = self._opt_tensor(index, (M,), "index", t.int32, who)
+        if stats is None:
+            stats = t.empty((8,), dtype=t.float32, device=self.device)
+        st = self._opt_tensor(stats, (8,), "stats", who=who)
+        ws = self._workspace()
+        self._keep_bc = (theta, o, a, w, y, ix, mean, scale)
+        self._check(self.lib.hg_bc_grad(self._h, _ptr(theta), _ptr(mean), _ptr(scale), _ptr(o), _ptr(a), _ptr(w), _ptr(y),
+                                        B, _ptr(ix), M, m, vf_coef, ent_coef, _ptr(grad), _ptr(st), _ptr(ws),
+                                        self._stream()))
+        return grad, st
+
+    def bc_update(self, params, state, obs, target, weight=None, value_target=None, epochs=4, minibatches=4, seed=0,
+                  mode="nll", vf_coef=0.0, ent_coef=0.0, obs_mean=None, obs_scale=None, lr=3e-4, betas=(0.9, 0.999),
+                  eps=1e-8, max_grad_norm=None, lr_dev=None, stats=None, index=None, publish=True):
+        """ppo_update's loop with bc_grad as the gradient (hg_bc_update): `epochs` fresh permutations of the B
+        rows, `minibatches` slices each, bc_grad then ppo_adam per slice, one call, no host decision in
+        between.  The rows and the loss's arguments are bc_grad's, the optimiser's ppo_adam's (there is no
+        KL early stop: this loss has no KL).  Returns the statistics rows [epochs * minibatches, 8].
+        publish=True ends with set_policy_theta(params, obs_mean, obs_scale): the env acts with the
+        distilled weights.  Bitwise the same calls made one by one; capturable."""
+        t = self.torch
+        who = "bc_update"
+        theta = self._opt_tensor(getattr(params, "theta", None), (_abi.HG_PPO_N_PARAMS,), "params.theta", who=who)
+        grad = self._opt_tensor(getattr(params, "grad", None), (_abi.HG_PPO_N_PARAMS,), "params.grad", who=who)
+        s = self._opt_state(state, who)
+        B, o, a, w, y, mean, scale, m, vf_coef, ent_coef = self._bc_rows(who, obs, target, weight, value_target, mode,
+                                                                         vf_coef, ent_coef, obs_mean, obs_scale)
+        epochs, minibatches = int(epochs), int(minibatches)
+        if epochs < 1:
+            raise ValueError(f"bc_update: epochs must be >= 1, got {epochs}")
+        if minibatches < 1 or minibatches > B:
+            raise ValueError(f"bc_update: minibatches must be in 1 .. {B} (the rows), got {minibatches}")
+        cfg = self._opt_cfg(who, lr, betas, eps, max_grad_norm, None, lr_dev)
+        if stats is None:
+            stats = getattr(self, "_bc_update_stats", None)
+            if stats is None or tuple(stats.shape) != (epochs * minibatches, 8):
+                stats = self._bc_update_stats = t.empty((epochs * minibatches, 8), dtype=t.float32, device=self.device)
+        st = self._opt_tensor(stats, (epochs * minibatches, 8), "stats", who=who)
+        if index is None:
+            index = getattr(self, "_ppo_update_index", None)
+            if index is None or tuple(index.shape) != (B,):
+                index = self._ppo_update_index = t.empty((B,), dtype=t.int32, device=self.device)
+        ix = self._opt_tensor(index, (B,), "index", t.int32, who)
+        ws = self._workspace()
+        self._keep_bc_update = (theta, grad, s, o, a, w, y, mean, scale, st, ix, lr_dev)
+        self._check(self.lib.hg_bc_update(self._h, _ptr(theta), _ptr(mean), _ptr(scale), _ptr(o), _ptr(a), _ptr(w), _ptr(y),
+                                          B, m, vf_coef, ent_coef, _ptr(grad), _ptr(ws), epochs, minibatches,
+                                          int(seed) & (2 ** 64 - 1), _ptr(ix), _ptr(st), _ptr(s), ctypes.byref(cfg),
+                                          self._stream()))
         if publish:
             self.set_policy_theta(params, mean, scale)
         return st
@@ -1072,6 +1174,29 @@ class HeliVecEnv(*_VEC_BASES):
         self._keep_plan = (a, g)
         self._check(self.lib.hg_mppi_update(self._h, _ptr(a), _ptr(g), H, B, float(lam), _ptr(o), self._stream()))
         return o
+
+    def mppi_value(self, returns, branches, lam, out=None):
+        """What mppi_update's weights make of the returns themselves (hg_mppi_value): for `returns`
+        [N, branches] a dict of value [N], the softmax-weighted mean return; best [N], the largest finite
+        return; ess [N], the weights' effective sample size (sum w)^2 / sum w^2.  A non-finite return weighs
+        0; an env without a finite one gets (0, -inf, 0).  `out`: such a dict to reuse."""
+        t = self.torch
+        N = self.num_envs
+        B = self._plan_count(branches, "branches")
+        lam = float(lam)
+        if not (np.isfinite(lam) and lam > 0):
+            raise ValueError(f"lam must be finite and > 0, got {lam!r}")
+        if not isinstance(returns, t.Tensor) or returns.ndim != 2:
+            raise ValueError(f"returns must be a [{N}, {B}] tensor")
+        g = self._plan_tensor(returns, (N, B), "returns")
+        if out is None:
+            out = {k: t.empty((N,), dtype=t.float32, device=self.device) for k in ("value", "best", "ess")}
+        v = self._plan_tensor(out["value"], (N,), "out['value']")
+        b = self._plan_tensor(out["best"], (N,), "out['best']")
+        s = self._plan_tensor(out["ess"], (N,), "out['ess']")
+        self._keep_plan = g
+        self._check(self.lib.hg_mppi_value(self._h, _ptr(g), B, lam, _ptr(v), _ptr(b), _ptr(s), self._stream()))
+        return out
 
     # ------------------------------------------------------------------ policy-guided planning
     def _act_bounds(self, lo, hi):

@@ -410,6 +410,52 @@ int32_t hg_ppo_grad(hg_env* env, const float* theta_dev,           /* [5641] the
                     float* stats_dev,     /* [8] out or NULL */
                     void* workspace_dev, void* stream);
 
+/* ---- The supervised half: the weighted imitation loss's gradient, the same kernel with a second loss head.
+ *
+ * For a caller that holds states, better actions and better return estimates -- a planner's (hg_mppi_value),
+ * a hand-written controller's, logged flights: behaviour cloning, DAgger / expert iteration,
+ * advantage-weighted regression.  theta's layout, the rows (index_dev[0..M) into the B stored rows, or
+ * 0..B-1 with index_dev NULL and M == B) and x, h1, h2, mu, v are hg_ppo_grad's, computed by the same code:
+ *   z_c  = (a*_i,c - mu_c) * exp(-log_std_c)
+ *   logp = -1/2 sum z^2 - sum log_std - 2 ln(2 pi)             (hg_ppo_grad's expression, the same fma chain)
+ *   mode HG_BC_NLL:  l_i = -logp                                (log_std is trained)
+ *   mode HG_BC_MSE:  l_i = 1/2 sum_c (a*_i,c - mu_c)^2          (log_std sees only the entropy term)
+ *   L = (1/M) sum_i [ w_i l_i + vf_coef * 1/2 (v - y_i)^2 ] - ent_coef * H,   H = sum log_std + 2 (1 + ln(2 pi))
+ * target_dev [B,4]: the actions a*, 16-byte aligned.
+ * weight_dev [B] or NULL (w = 1, bitwise a tensor of ones).  The weights are used as given: a negative one
+ *   pushes away from its target, a non-finite one gives a non-finite gradient, which hg_ppo_adam's guard
+ *   drops.  The value term is unweighted.
+ * value_target_dev [B], the y, or NULL: NULL requires vf_coef == 0; the pointer is then never read, the
+ *   value term is 0 and so is stats[1].
+ * grad_dev [HG_PPO_N_PARAMS] = dL/dtheta in theta's layout, overwritten.  Per sample, with g = -w_i / M:
+ *   NLL: dL/dmu_c = g z_c exp(-log_std_c), dL/dlog_std_c += g (z_c^2 - 1);   MSE: dL/dmu_c = -(a*_c - mu_c) w_i / M
+ *   and nothing on log_std, whose gradient is then -ent_coef bitwise.  dL/dv = vf_coef (v - y_i) / M.
+ * stats_dev [8] or NULL:  [0] mean w l  [1] mean 1/2 (v - y)^2  [2] mean sum_c (a* - mu)^2, unweighted, in
+ *   both modes  [3] mean w  [4] H  [5] L = [0] + vf_coef [1] - ent_coef H  [6] mean logp(a*), unweighted
+ *   [7] skipped index entries, as a float.  (hg_ppo_grad's reduction, unchanged: five sums times 1/M.)  In
+ *   mode HG_BC_NLL with weight_dev NULL, [0] == -[6] bitwise.
+ * Everything else is hg_ppo_grad's: fp32 and exact fma chains on the fp32 matrix instruction; out-of-range
+ * index entries skipped and counted, the means still dividing by M; asynchronous on `stream`, allocates
+ * nothing, capturable, theta_dev read when the kernel runs; deterministic (no atomics, partial sums through
+ * workspace_dev, hg_ppo_grad_workspace_bytes() bytes, added in a fixed order; the launch shape a function of
+ * M and compile-time constants); the env is not modified.
+ * HG_E_INVALID, outputs untouched: NULL env; a NULL or misaligned (4 bytes; target_dev and workspace_dev
+ * 16) required pointer; a misaligned optional one; B < 1; M < 1; M > 2^31 - 256; index_dev NULL with
+ * M != B; a mode outside the enum; a non-finite or negative vf_coef or ent_coef; value_target_dev NULL with
+ * vf_coef != 0. */
+enum { HG_BC_NLL = 0, HG_BC_MSE = 1 };
+
+int32_t hg_bc_grad(hg_env* env, const float* theta_dev,            /* [5641] the LEARNER's current weights */
+                   const float* obs_mean_dev, const float* obs_scale_dev,    /* [17] or NULL (0 / 1); constants */
+                   const float* obs_dev, const float* target_dev,            /* [B,17], [B,4] (16-byte aligned) */
+                   const float* weight_dev,                                  /* [B] or NULL: w = 1 */
+                   const float* value_target_dev,                            /* [B] or NULL: needs vf_coef == 0 */
+                   int64_t B, const int32_t* index_dev, int64_t M,            /* minibatch rows, or NULL: M == B, rows 0..B-1 */
+                   int32_t mode, float vf_coef, float ent_coef,
+                   float* grad_dev,      /* [5641] out, overwritten (not accumulated) */
+                   float* stats_dev,     /* [8] out or NULL */
+                   void* workspace_dev, void* stream);
+
 /* ---- The update phase on the device: minibatch shuffle, gradient clipping, Adam, and all of it in one call.
  *
  * Every call below is asynchronous on `stream`, allocates nothing, makes no host decision that depends on
@@ -506,6 +552,21 @@ int32_t hg_ppo_update(hg_env* env, float* theta_dev, const float* obs_mean_dev, 
                       const float* ret_dev, int64_t B, float clip, float vf_coef, float ent_coef, float* grad_dev,
                       void* workspace_dev, int32_t n_epochs, int32_t n_minibatches, uint64_t seed, int32_t* index_dev,
                       float* stats_out_dev, void* state_dev, const hg_ppo_opt_cfg* cfg, void* stream);
+
+/* hg_ppo_update's loop with hg_bc_grad as the gradient: the same optimiser state, cfg, slice rule, index_dev
+ * scratch and stats_out_dev [n_epochs * n_minibatches, 8] (hg_bc_grad's rows, or NULL); the arguments up to
+ * workspace_dev are hg_bc_grad's.
+ *   stop = 0;  for each epoch: hg_ppo_shuffle keyed on the state's `seen` word;  for each minibatch:
+ *   hg_bc_grad over the slice, then hg_ppo_adam with cfg's target_kl taken as 0.
+ * The results are bitwise those of the same calls made one by one.  cfg->target_kl > 0 is refused: the
+ * optimiser's early stop reads stats[2], which is a squared action error here, not a KL.
+ * HG_E_INVALID before anything is enqueued: what hg_ppo_shuffle, hg_bc_grad and hg_ppo_adam refuse;
+ * target_kl > 0; n_epochs < 1; n_minibatches outside 1 .. B. */
+int32_t hg_bc_update(hg_env* env, float* theta_dev, const float* obs_mean_dev, const float* obs_scale_dev,
+                     const float* obs_dev, const float* target_dev, const float* weight_dev,
+                     const float* value_target_dev, int64_t B, int32_t mode, float vf_coef, float ent_coef,
+                     float* grad_dev, void* workspace_dev, int32_t n_epochs, int32_t n_minibatches, uint64_t seed,
+                     int32_t* index_dev, float* stats_out_dev, void* state_dev, const hg_ppo_opt_cfg* cfg, void* stream);
 
 /* Publish the learner's weights to the env: hg_set_policy + hg_set_value_head on the tensors of a flat
  * theta_dev [5641] (log_std included: a stochastic policy), bitwise those two calls.  obs_mean_dev /
@@ -666,6 +727,21 @@ int32_t hg_mppi_sample(hg_env* env, const float* nominal_dev, int32_t horizon, i
  * rows.  lambda > 0.  nominal_out_dev [horizon, N, 4] may not overlap actions_dev. */
 int32_t hg_mppi_update(hg_env* env, const float* actions_dev, const float* return_dev, int32_t horizon,
                        int32_t branches, float lambda, float* nominal_out_dev, void* stream);
+
+/* What the planner thinks each env's state is worth: hg_mppi_update's weights applied to the returns
+ * themselves.  return_dev [N, branches]; per env, with w_b and G_max exactly hg_mppi_update's (the same
+ * exp2((G_b - G_max) * (log2(e) / lambda)), 0 for a non-finite G_b):
+ *   value[e] = (sum_b w_b G_b) / (sum_b w_b),  num = fma(w_b, G_b, num) and den = den + w_b over b ascending:
+ *              the chain hg_mppi_update runs on an action column (a non-finite G_b enters as 0 times 0);
+ *   best[e]  = G_max                                       (best_dev [N] or NULL);
+ *   ess[e]   = den^2 / sum_b w_b^2, sq = fma(w_b, w_b, sq)  (ess_dev [N] or NULL): the effective sample size.
+ * An env with no finite return gets value 0, best -inf, ess 0.  With hg_rollout_branch_policy's
+ * HG_BOOTSTRAP_VALUE returns, value is the planner's n-step lookahead value: hg_bc_grad's value_target_dev.
+ * One wave per env; asynchronous, capturable, the env is not modified.
+ * HG_E_INVALID, outputs untouched: branches outside hg_mppi_update's range; lambda not > 0 (or
+ * log2(e) / lambda not finite in fp32); NULL return_dev or value_dev; a misaligned (4 bytes) pointer; NULL env. */
+int32_t hg_mppi_value(hg_env* env, const float* return_dev, int32_t branches, float lambda, float* value_dev,
+                      float* best_dev, float* ess_dev, void* stream);
 
 /* ---- Policy-guided planning: the handle's policy inside the branches, its value head behind them.
  *
