@@ -29,6 +29,7 @@
 #include "ppo_grad.h"
 #include "ppo_opt.h"
 #include "rollout_stats.h"
+#include "es.h"
 #include "retrim_body.h"
 #include "baked.h"
 
@@ -1116,6 +1117,21 @@ __global__ __launch_bounds__(64, 1) void rollout_policy_kernel(float* __restrict
                                                                const PolicyArgs pol) {
     step_body<TASK, ETA, true, FEAT, true, BAKED, false, 0, true>(state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x,
                                                                   pol);
+}
+
+// hg_rollout_pop: rollout_policy_kernel (in-kernel noise) in which the wave of state tile t reads the packed
+// image of member t / tiles_per_member of a caller-owned population [P, kPolicyFloats].  The offset is
+// block-uniform scalar arithmetic on a copy of `pol`; step_body is the same instantiation's code.  An
+// argument of its own after `pol`: no existing kernel's argument segment moves.
+template <int TASK, bool FEAT, bool BAKED>
+__global__ __launch_bounds__(64, 1) void rollout_pop_kernel(float* __restrict__ state_p, int64_t n_p, uint64_t seed_p,
+                                                            int64_t envoff_p, ParamArg Pa,
+                                                            const Template<float>* __restrict__ Tp, const StepArgs a,
+                                                            const PolicyArgs pol, const uint32_t tiles_per_member) {
+    PolicyArgs mine = pol;
+    mine.pk = pol.pk + (size_t)(blockIdx.x / tiles_per_member) * hgp::kPolicyFloats;
+    step_body<TASK, false, true, FEAT, true, BAKED, false, 0, true>(state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x,
+                                                                    mine);
 }
 
 // hg_rollout_ac: rollout_policy_kernel with the log-probabilities and the value head's values (step_body's
@@ -2343,6 +2359,24 @@ static void launch_rollout_policy(const hg_env* e, hipStream_t s, const StepArgs
         else eta ? go(rollout_policy_kernel<T, true, false, false>) : go(rollout_policy_kernel<T, false, false, false>);
     }
 }
+// hg_rollout_pop's launch: task x optional features x the constant-specialised step
+template <int T>
+static void launch_rollout_pop(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol, uint32_t tiles,
+                               bool feat) {
+    const unsigned grid = (unsigned)((e->n + 63) / 64);
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, STEP_KARGS(e), a, pol, tiles); };
+    ++e->n_launch[4];
+    if (e->baked) feat ? go(rollout_pop_kernel<T, true, true>) : go(rollout_pop_kernel<T, false, true>);
+    else feat ? go(rollout_pop_kernel<T, true, false>) : go(rollout_pop_kernel<T, false, false>);
+}
+static void dispatch_rollout_pop(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol, uint32_t tiles,
+                                 bool feat) {
+    switch (e->cfg.task) {
+        case HG_TASK_HOVER: launch_rollout_pop<HG_TASK_HOVER>(e, s, a, pol, tiles, feat); break;
+        case HG_TASK_FORWARD_FLIGHT: launch_rollout_pop<HG_TASK_FORWARD_FLIGHT>(e, s, a, pol, tiles, feat); break;
+        default: launch_rollout_pop<HG_TASK_HELI>(e, s, a, pol, tiles, feat); break;
+    }
+}
 // hg_rollout_ac's launch, as hg_rollout_policy's
 template <int T>
 static void launch_rollout_ac(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol, const AcArgs& ac,
@@ -3529,6 +3563,183 @@ int32_t hg_set_policy_theta(hg_env* e, const float* theta, const float* obs_mean
                                      stream);
     if (rc != HG_OK) return rc;
     return hg_set_value_head(e, theta + hgk::kPpoWv, theta + hgk::kPpoBv, stream);
+}
+
+// ---- populations and evolution strategies (the kernels: es.hip; the rollout: rollout_pop_kernel above)
+int64_t hg_policy_image_floats(void) { return hgp::kPolicyFloats; }
+
+int64_t hg_es_workspace_bytes(int64_t P) {
+    if (P < 2 || (P & 1) || P > hgk::kEsMaxPop) return HG_E_INVALID;
+    return hgk::es_workspace_bytes(P);
+}
+
+int32_t hg_pop_pack(hg_env* e, const float* theta, int64_t P, int32_t stochastic, const float* obs_mean,
+                    const float* obs_scale, float* images, void* stream) {
+    if (!theta || !images) return fail(HG_E_INVALID, "hg_pop_pack: theta and images must be device pointers");
+    if ((((uintptr_t)theta | (uintptr_t)obs_mean | (uintptr_t)obs_scale) & 3) != 0 || ((uintptr_t)images & 15) != 0)
+        return fail(HG_E_INVALID, "hg_pop_pack: images must be 16-byte aligned, the other pointers 4-byte");
+    if (P < 1 || P > 65536) return fail(HG_E_INVALID, "hg_pop_pack: P must be in 1 .. 65536");
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    HIP_TRY(hgk::launch_pop_pack(theta, P, stochastic != 0, obs_mean, obs_scale, images, (hipStream_t)stream));
+    return HG_OK;
+}
+
+int32_t hg_rollout_pop(hg_env* e, const float* images, int64_t P, int64_t envs_per_member, const float* obs0,
+                       int32_t nsteps, float* actions_out, float* obs, float* reward, uint8_t* terminated,
+                       uint8_t* truncated, uint8_t* info, void* stream) {
+    if (nsteps < 1) return fail(HG_E_INVALID, "nsteps must be >= 1");
+    if (!images || !obs0 || !actions_out || !obs || !reward || !terminated || !truncated)
+        return fail(HG_E_INVALID, "images/obs0/actions_out/obs/reward/terminated/truncated must be device pointers");
+    if (((uintptr_t)images & 15) || ((uintptr_t)actions_out & 15) || ((uintptr_t)obs & 15))
+        return fail(HG_E_INVALID, "images, actions_out and obs must be 16-byte aligned");
+    if (P < 1 || P > 65536) return fail(HG_E_INVALID, "hg_rollout_pop: P must be in 1 .. 65536");
+    if (envs_per_member < 64 || (envs_per_member & 63) || envs_per_member > ((int64_t)1 << 37))
+        return fail(HG_E_INVALID, "hg_rollout_pop: envs_per_member must be a positive multiple of 64");
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!((P - 1) * envs_per_member < e->n && e->n <= P * envs_per_member))
+        return fail(HG_E_INVALID, "hg_rollout_pop: need (P - 1) * envs_per_member < num_envs <= P * envs_per_member");
+    if (e->Pf.reset_retrim && e->Pf.autoreset)
+        return fail(HG_E_INVALID, "hg_rollout_pop does not support auto-resets in reset_mode RETRIM (re-trims run between steps)");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    e->ov_chain = kChainBroken;   // the next step's pending resets take the serial re-trim
+    e->chain_expect = kChainBroken;
+    StepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.hmap = e->hmap;
+    a.obs = obs;
+    a.reward = reward;
+    a.terminated = terminated;
+    a.truncated = truncated;
+    a.info = info;
+    a.tmpl_env = e->tmpl_env;
+    a.nsteps = nsteps;
+    a.retrim_slot = -1;
+    a.retrim_wind = e->retrim_wind;   // (reset_mode RETRIM without auto-reset: as hg_rollout)
+    PolicyArgs pol;
+    pol.pk = images;
+    pol.obs0 = obs0;
+    pol.actions_out = actions_out;
+    const bool feat = e->Pf.autoreset_next || e->Pf.max_episode_steps != INT32_MAX || e->Pf.env_templates ||
+                      e->Pf.reset_retrim;
+    dispatch_rollout_pop(e, (hipStream_t)stream, a, pol, (uint32_t)(envs_per_member / 64), feat);
+    HIP_TRY(hipGetLastError());
+    return HG_OK;
+}
+
+static hgk::EsNoiseKey es_key(uint64_t seed, int64_t gen, const int32_t* gen_dev) {
+    return hgk::EsNoiseKey{(uint32_t)seed ^ hgk::kEsKey0, (uint32_t)(seed >> 32) ^ hgk::kEsKey1, gen, gen_dev};
+}
+
+int32_t hg_es_perturb(hg_env* e, const float* theta, int64_t P, float sigma, uint64_t seed, int64_t gen,
+                      const int32_t* gen_dev, int32_t stochastic, const float* obs_mean, const float* obs_scale,
+                      float* images, float* member_theta, void* stream) {
+    if (!theta || !images) return fail(HG_E_INVALID, "hg_es_perturb: theta and images must be device pointers");
+    if ((((uintptr_t)theta | (uintptr_t)obs_mean | (uintptr_t)obs_scale | (uintptr_t)gen_dev | (uintptr_t)member_theta) & 3) != 0 ||
+        ((uintptr_t)images & 15) != 0)
+        return fail(HG_E_INVALID, "hg_es_perturb: images must be 16-byte aligned, the other pointers 4-byte");
+    if (P < 2 || (P & 1) || P > 65536) return fail(HG_E_INVALID, "hg_es_perturb: P must be even, in 2 .. 65536");
+    if (!std::isfinite(sigma) || !(sigma > 0.f)) return fail(HG_E_INVALID, "hg_es_perturb: sigma must be finite and > 0");
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    HIP_TRY(hgk::launch_es_perturb(theta, P, sigma, es_key(seed, gen, gen_dev), stochastic != 0, obs_mean, obs_scale, images,
+                                   member_theta, (hipStream_t)stream));
+    return HG_OK;
+}
+
+int32_t hg_es_noise(hg_env* e, uint64_t seed, int64_t gen, const int32_t* gen_dev, int64_t pair, float* out, void* stream) {
+    if (!out) return fail(HG_E_INVALID, "hg_es_noise: out must be a device pointer");
+    if ((((uintptr_t)out | (uintptr_t)gen_dev) & 3) != 0) return fail(HG_E_INVALID, "hg_es_noise: out and gen_dev must be 4-byte aligned");
+    if (pair < 0 || pair >= 32768) return fail(HG_E_INVALID, "hg_es_noise: pair must be in 0 .. 32767");
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    HIP_TRY(hgk::launch_es_noise(es_key(seed, gen, gen_dev), (uint32_t)pair, out, (hipStream_t)stream));
+    return HG_OK;
+}
+
+int32_t hg_pop_fitness(hg_env* e, const float* reward, const uint8_t* terminated, const uint8_t* truncated, int32_t K,
+                       int64_t P, int64_t envs_per_member, int32_t mode, int32_t restart, uint8_t* alive, double* sum,
+                       float* fitness_out, void* stream) {
+    if (!reward || !sum || !fitness_out) return fail(HG_E_INVALID, "hg_pop_fitness: reward/sum/fitness_out must be device pointers");
+    if (mode != HG_POP_FIT_WINDOW && mode != HG_POP_FIT_FIRST_EPISODE) return fail(HG_E_INVALID, "hg_pop_fitness: unknown mode");
+    if (mode == HG_POP_FIT_FIRST_EPISODE && (!terminated || !truncated || !alive))
+        return fail(HG_E_INVALID, "hg_pop_fitness: HG_POP_FIT_FIRST_EPISODE needs terminated, truncated and alive");
+    if ((((uintptr_t)reward | (uintptr_t)fitness_out) & 3) != 0 || ((uintptr_t)sum & 7) != 0)
+        return fail(HG_E_INVALID, "hg_pop_fitness: reward and fitness_out must be 4-byte aligned, sum 8-byte");
+    if (K < 1) return fail(HG_E_INVALID, "hg_pop_fitness: K must be >= 1");
+    if (P < 1 || P > 65536) return fail(HG_E_INVALID, "hg_pop_fitness: P must be in 1 .. 65536");
+    if (envs_per_member < 64 || (envs_per_member & 63) || envs_per_member > ((int64_t)1 << 37))
+        return fail(HG_E_INVALID, "hg_pop_fitness: envs_per_member must be a positive multiple of 64");
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!((P - 1) * envs_per_member < e->n && e->n <= P * envs_per_member))
+        return fail(HG_E_INVALID, "hg_pop_fitness: need (P - 1) * envs_per_member < num_envs <= P * envs_per_member");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    hgk::PopFitnessArgs a;
+    a.reward = reward;
+    a.terminated = terminated;
+    a.truncated = truncated;
+    a.N = e->n;
+    a.epm = envs_per_member;
+    a.K = K;
+    a.first_episode = mode == HG_POP_FIT_FIRST_EPISODE;
+    a.restart = restart != 0;
+    a.alive = alive;
+    a.sum = sum;
+    a.fitness = fitness_out;
+    HIP_TRY(hgk::launch_pop_fitness(a, P, (hipStream_t)stream));
+    return HG_OK;
+}
+
+int32_t hg_es_grad(hg_env* e, const float* fitness, int64_t P, float sigma, uint64_t seed, int64_t gen,
+                   const int32_t* gen_dev, float* grad, float* stats, void* workspace, void* stream) {
+    if (!fitness || !grad || !workspace) return fail(HG_E_INVALID, "hg_es_grad: fitness/grad/workspace must be device pointers");
+    if ((((uintptr_t)fitness | (uintptr_t)grad | (uintptr_t)stats | (uintptr_t)gen_dev) & 3) != 0 || ((uintptr_t)workspace & 15) != 0)
+        return fail(HG_E_INVALID, "hg_es_grad: workspace must be 16-byte aligned, the other pointers 4-byte");
+    if (P < 2 || (P & 1) || P > hgk::kEsMaxPop) return fail(HG_E_INVALID, "hg_es_grad: P must be even, in 2 .. 16384");
+    if (!std::isfinite(sigma) || !(sigma > 0.f)) return fail(HG_E_INVALID, "hg_es_grad: sigma must be finite and > 0");
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    hgk::EsGradArgs a;
+    a.fitness = fitness;
+    a.P = (int32_t)P;
+    a.scale = (float)(-1.0 / ((double)P * (double)sigma));
+    a.key = es_key(seed, gen, gen_dev);
+    a.grad = grad;
+    a.stats = stats;
+    a.ws = (float*)workspace;
+    HIP_TRY(hgk::launch_es_grad(a, (hipStream_t)stream));
+    return HG_OK;
+}
+
+// Diagnostics (tests): the handle's own packed image out / in, a device-to-device copy on `stream`
+int32_t hg_debug_get_policy_image(hg_env* e, float* image_out, void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!image_out) return fail(HG_E_INVALID, "hg_debug_get_policy_image: image_out must be a device pointer");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    HIP_TRY(hipMemcpyAsync(image_out, e->policy_dev, sizeof(float) * hgp::kPolicyFloats, hipMemcpyDeviceToDevice,
+                           (hipStream_t)stream));
+    return HG_OK;
+}
+
+int32_t hg_debug_set_policy_image(hg_env* e, const float* image, void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!image) return fail(HG_E_INVALID, "hg_debug_set_policy_image: image must be a device pointer");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    e->ov_chain = kChainBroken;
+    e->chain_expect = kChainBroken;
+    HIP_TRY(hipMemcpyAsync(e->policy_dev, image, sizeof(float) * hgp::kPolicyFloats, hipMemcpyDeviceToDevice,
+                           (hipStream_t)stream));
+    e->policy_set = true;
+    e->value_set = true;
+    return HG_OK;
 }
 
 // ---- running normalisation and episode statistics (the kernels: rollout_stats.hip)

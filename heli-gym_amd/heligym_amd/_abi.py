@@ -32,6 +32,11 @@ HG_BC_NLL, HG_BC_MSE = 0, 1
 BC_MODES = {"nll": HG_BC_NLL, "mse": HG_BC_MSE}
 HG_ABI_VERSION = 3
 HG_PPO_N_PARAMS = 5641
+HG_POLICY_IMAGE_FLOATS = 7552   # hg_policy_image_floats()
+HG_ES_N_PERTURBED = 5572        # the actor-mean parameters: theta[0 .. 5572)
+HG_ES_MAX_POP = 16384           # hg_es_grad's population cap
+HG_POP_FIT_WINDOW, HG_POP_FIT_FIRST_EPISODE = 0, 1
+POP_FIT_MODES = {"window": HG_POP_FIT_WINDOW, "first_episode": HG_POP_FIT_FIRST_EPISODE}
 HG_PPO_OPT_STATE_BYTES = 45248
 
 AIRFRAME_FIELDS = (
@@ -148,6 +153,20 @@ _SIGS = {
                                       ctypes.c_float, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, _P, _P, _P,
                                       ctypes.POINTER(hg_ppo_opt_cfg), _P]),
     "hg_set_policy_theta": (ctypes.c_int32, [_P, _P, _P, _P, _P]),
+    "hg_policy_image_floats": (ctypes.c_int64, []),
+    "hg_pop_pack": (ctypes.c_int32, [_P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P, _P, _P]),
+    "hg_rollout_pop": (ctypes.c_int32, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int32, _P, _P, _P, _P, _P, _P,
+                                        _P]),
+    "hg_es_perturb": (ctypes.c_int32, [_P, _P, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64, ctypes.c_int64, _P,
+                                       ctypes.c_int32, _P, _P, _P, _P, _P]),
+    "hg_es_noise": (ctypes.c_int32, [_P, ctypes.c_uint64, ctypes.c_int64, _P, ctypes.c_int64, _P, _P]),
+    "hg_pop_fitness": (ctypes.c_int32, [_P, _P, _P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                        ctypes.c_int32, _P, _P, _P, _P]),
+    "hg_es_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64]),
+    "hg_es_grad": (ctypes.c_int32, [_P, _P, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64, ctypes.c_int64, _P, _P, _P, _P,
+                                    _P]),
+    "hg_debug_get_policy_image": (ctypes.c_int32, [_P, _P, _P]),
+    "hg_debug_set_policy_image": (ctypes.c_int32, [_P, _P, _P]),
     "hg_rollout_stats_state_bytes": (ctypes.c_int64, [ctypes.c_int64]),
     "hg_rollout_stats_init": (ctypes.c_int32, [_P, _P, _P]),
     "hg_rollout_stats": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int32,

@@ -1077,6 +1077,196 @@ class HeliVecEnv(*_VEC_BASES):
                                               _ptr(ro), _ptr(oi), _ptr(outs[3]), self._stream()))
         return stats
 
+    # ------------------------------------------------------------------ populations and evolution strategies
+    def _pop_count(self, P, who, even=False, cap=65536):
+        P = int(P)
+        if P < (2 if even else 1) or P > cap or (even and P % 2):
+            raise ValueError(f"{who}: the population must be {'even, ' if even else ''}in {2 if even else 1} .. {cap}, got {P}")
+        return P
+
+    def _pop_members(self, P, envs_per_member, who):
+        P, m = self._pop_count(P, who), int(envs_per_member)
+        if m < 64 or m % 64:
+            raise ValueError(f"{who}: envs_per_member must be a positive multiple of 64, got {m}")
+        if not (P - 1) * m < self.num_envs <= P * m:
+            raise ValueError(f"{who}: {P} members of {m} envs do not cover {self.num_envs} envs "
+                             f"(need (P - 1) * envs_per_member < num_envs <= P * envs_per_member)")
+        return P, m
+
+    def _pop_norm(self, obs_mean, obs_scale, who):
+        mean = None if obs_mean is None else self._opt_tensor(obs_mean, (_abi.HG_N_OBS,), "obs_mean", who=who)
+        scale = None if obs_scale is None else self._opt_tensor(obs_scale, (_abi.HG_N_OBS,), "obs_scale", who=who)
+        return mean, scale
+
+    def _gen_dev(self, gen_dev, who):
+        t = self.torch
+        if gen_dev is not None and (not isinstance(gen_dev, t.Tensor) or gen_dev.dtype != t.int32
+                                    or gen_dev.device != self.device or gen_dev.numel() != 1):
+            raise ValueError(f"{who}: gen_dev must be an int32 tensor of one element on {self.device}")
+        return gen_dev
+
+    def _sigma(self, sigma, who):
+        import math
+        sigma = float(sigma)
+        if not math.isfinite(sigma) or sigma <= 0:
+            raise ValueError(f"{who}: sigma must be finite and > 0, got {sigma}")
+        return sigma
+
+    def pop_pack(self, thetas, stochastic=True, obs_mean=None, obs_scale=None, out=None):
+        """P packed policy images [P, 7552] from P flat parameter vectors `thetas` [P, 5641] in one launch
+        (hg_pop_pack): image p is bitwise what set_policy_theta of thetas[p] leaves in a handle, value head
+        included; stochastic=False gives deterministic policies (set_policy without log_std).  obs_mean /
+        obs_scale [17] are shared.  `out`: a float32 [P, 7552] tensor to reuse."""
+        t = self.torch
+        if not isinstance(thetas, t.Tensor) or thetas.ndim != 2:
+            raise ValueError("pop_pack: thetas must be a [P, 5641] tensor")
+        P = self._pop_count(thetas.shape[0], "pop_pack")
+        th = self._opt_tensor(thetas, (P, _abi.HG_PPO_N_PARAMS), "thetas", who="pop_pack")
+        mean, scale = self._pop_norm(obs_mean, obs_scale, "pop_pack")
+        if out is None:
+            out = t.empty((P, _abi.HG_POLICY_IMAGE_FLOATS), dtype=t.float32, device=self.device)
+        out = self._opt_tensor(out, (P, _abi.HG_POLICY_IMAGE_FLOATS), "out", who="pop_pack")
+        self._keep_pop_pack = (th, mean, scale)
+        self._check(self.lib.hg_pop_pack(self._h, _ptr(th), P, 1 if stochastic else 0, _ptr(mean), _ptr(scale), _ptr(out),
+                                         self._stream()))
+        return out
+
+    def rollout_population(self, K, images, envs_per_member, obs0=None, out=None):
+        """rollout_policy with one policy per block of `envs_per_member` consecutive envs (hg_rollout_pop):
+        member p, image images[p] of a [P, 7552] population (pop_pack, es_perturb), drives envs
+        p * envs_per_member .. ; the last member may be short.  Same outputs as rollout_policy, member p's
+        rows bitwise those of a separate handle with that policy.  The env's own policy is not used."""
+        t = self.torch
+        K, N = int(K), self.num_envs
+        if not isinstance(images, t.Tensor) or images.ndim != 2:
+            raise ValueError("rollout_population: images must be a [P, 7552] tensor")
+        P, m = self._pop_members(images.shape[0], envs_per_member, "rollout_population")
+        im = self._opt_tensor(images, (P, _abi.HG_POLICY_IMAGE_FLOATS), "images", who="rollout_population")
+        o0 = self._obs_arg(obs0, "obs0")
+        if out is None or out[0].shape[0] != K:
+            out = (t.empty((K, N, _abi.HG_N_ACT), dtype=t.float32, device=self.device),
+                   t.empty((K, N, _abi.HG_N_OBS), dtype=t.float32, device=self.device),
+                   t.empty((K, N), dtype=t.float32, device=self.device),
+                   t.empty((K, N), dtype=t.uint8, device=self.device),
+                   t.empty((K, N), dtype=t.uint8, device=self.device),
+                   t.empty((K, N), dtype=t.uint8, device=self.device))
+        act, obs, rew, term, trunc, info = out
+        self._keep_pop = (o0, im)
+        self._check(self.lib.hg_rollout_pop(self._h, _ptr(im), P, m, _ptr(o0), K, _ptr(act), _ptr(obs), _ptr(rew),
+                                            _ptr(term), _ptr(trunc), _ptr(info), self._stream()))
+        return out
+
+    def es_perturb(self, params, population, sigma, seed, gen=0, gen_dev=None, stochastic=True, obs_mean=None,
+                   obs_scale=None, out=None, member_theta=None):
+        """The images [P, 7552] of an antithetic ES population around params.theta (or a flat tensor; hg_es_perturb): members
+        2j and 2j+1 are theta +- sigma eps_j on the 5572 actor-mean parameters, eps from counters keyed by
+        (seed, pair, gen + *gen_dev) and never stored.  member_theta: a float32 [P, 5641] tensor that also
+        receives the members' parameter vectors.  Returns the images."""
+        t = self.torch
+        theta = params if isinstance(params, t.Tensor) else getattr(params, "theta", None)
+        theta = self._opt_tensor(theta, (_abi.HG_PPO_N_PARAMS,), "params.theta", who="es_perturb")
+        P = self._pop_count(population, "es_perturb", even=True)
+        sigma = self._sigma(sigma, "es_perturb")
+        gd = self._gen_dev(gen_dev, "es_perturb")
+        mean, scale = self._pop_norm(obs_mean, obs_scale, "es_perturb")
+        if out is None:
+            out = t.empty((P, _abi.HG_POLICY_IMAGE_FLOATS), dtype=t.float32, device=self.device)
+        out = self._opt_tensor(out, (P, _abi.HG_POLICY_IMAGE_FLOATS), "out", who="es_perturb")
+        mt = None if member_theta is None else self._opt_tensor(member_theta, (P, _abi.HG_PPO_N_PARAMS), "member_theta",
+                                                                who="es_perturb")
+        self._keep_es_perturb = (theta, gd, mean, scale, mt)
+        self._check(self.lib.hg_es_perturb(self._h, _ptr(theta), P, sigma, int(seed) & (2 ** 64 - 1), int(gen), _ptr(gd),
+                                           1 if stochastic else 0, _ptr(mean), _ptr(scale), _ptr(out), _ptr(mt),
+                                           self._stream()))
+        return out
+
+    def es_noise(self, seed, pair, gen=0, gen_dev=None, out=None):
+        """eps_pair [5572] as es_perturb and es_grad compute it (hg_es_noise; a diagnostic, like debug_eta)."""
+        t = self.torch
+        gd = self._gen_dev(gen_dev, "es_noise")
+        if out is None:
+            out = t.empty((_abi.HG_ES_N_PERTURBED,), dtype=t.float32, device=self.device)
+        out = self._opt_tensor(out, (_abi.HG_ES_N_PERTURBED,), "out", who="es_noise")
+        self._keep_es_noise = gd
+        self._check(self.lib.hg_es_noise(self._h, int(seed) & (2 ** 64 - 1), int(gen), _ptr(gd), int(pair), _ptr(out),
+                                         self._stream()))
+        return out
+
+    def pop_fitness(self, reward, terminated, truncated, population, envs_per_member, sums, mode="window", restart=False,
+                    alive=None, out=None):
+        """Per-member fitness of a population rollout's rewards [K, N] (hg_pop_fitness), accumulated across
+        calls in `sums` (float64 [P]): mode "window" counts every reward, "first_episode" each env's rewards
+        up to its first terminated | truncated since the last restart (`alive`: uint8 [N], required).
+        restart=True clears sums and alive first.  Returns out (float32 [P]) = sums / member env count."""
+        t = self.torch
+        if mode not in _abi.POP_FIT_MODES:
+            raise ValueError(f"pop_fitness: mode must be one of {sorted(_abi.POP_FIT_MODES)}, got {mode!r}")
+        P, m = self._pop_members(population, envs_per_member, "pop_fitness")
+        if not isinstance(reward, t.Tensor) or reward.ndim != 2:
+            raise ValueError("pop_fitness: reward must be a [K, N] tensor")
+        K, N = int(reward.shape[0]), self.num_envs
+        r = self._opt_tensor(reward, (K, N), "reward", who="pop_fitness")
+        first = mode == "first_episode"
+        te = None if terminated is None and not first else self._opt_tensor(terminated, (K, N), "terminated", t.uint8,
+                                                                            "pop_fitness")
+        tr = None if truncated is None and not first else self._opt_tensor(truncated, (K, N), "truncated", t.uint8,
+                                                                           "pop_fitness")
+        if first and alive is None:
+            raise ValueError("pop_fitness: mode 'first_episode' needs alive (uint8 [N])")
+        al = None if alive is None else self._opt_tensor(alive, (N,), "alive", t.uint8, "pop_fitness")
+        s = self._opt_tensor(sums, (P,), "sums", t.float64, "pop_fitness")
+        if out is None:
+            out = t.empty((P,), dtype=t.float32, device=self.device)
+        out = self._opt_tensor(out, (P,), "out", who="pop_fitness")
+        self._keep_pop_fit = (r, te, tr, al, s)
+        self._check(self.lib.hg_pop_fitness(self._h, _ptr(r), _ptr(te), _ptr(tr), K, P, m, _abi.POP_FIT_MODES[mode],
+                                            1 if restart else 0, _ptr(al), _ptr(s), _ptr(out), self._stream()))
+        return out
+
+    def _es_workspace(self, P):
+        ws = getattr(self, "_es_ws", None)
+        need = int(self.lib.hg_es_workspace_bytes(P))
+        if ws is None or ws.numel() < need:
+            ws = self._es_ws = self.torch.empty((need,), dtype=self.torch.uint8, device=self.device)
+        return ws
+
+    def es_grad(self, params, fitness, sigma, seed, gen=0, gen_dev=None, stats=None):
+        """The ES gradient estimate into params.grad (or a flat tensor; hg_es_grad): centred ranks of `fitness` [P] (non-finite
+        ones rank lowest), grad = -1/(P sigma) sum_j (u_2j - u_2j+1) eps_j with eps regenerated from
+        es_perturb's counters, zero outside the 5572 perturbed parameters; ppo_adam on it ascends the fitness.
+        Returns (params.grad, stats [8]: mean, min, max of the finite fitnesses, non-finite count, best index,
+        gradient norm, 0, 0).  The workspace is allocated once per population size, before any capture."""
+        t = self.torch
+        grad = params if isinstance(params, t.Tensor) else getattr(params, "grad", None)
+        grad = self._opt_tensor(grad, (_abi.HG_PPO_N_PARAMS,), "params.grad", who="es_grad")
+        if not isinstance(fitness, t.Tensor) or fitness.ndim != 1:
+            raise ValueError("es_grad: fitness must be a [P] tensor")
+        P = self._pop_count(fitness.shape[0], "es_grad", even=True, cap=_abi.HG_ES_MAX_POP)
+        f = self._opt_tensor(fitness, (P,), "fitness", who="es_grad")
+        sigma = self._sigma(sigma, "es_grad")
+        gd = self._gen_dev(gen_dev, "es_grad")
+        if stats is None:
+            stats = t.empty((8,), dtype=t.float32, device=self.device)
+        st = self._opt_tensor(stats, (8,), "stats", who="es_grad")
+        ws = self._es_workspace(P)
+        self._keep_es_grad = (f, gd)
+        self._check(self.lib.hg_es_grad(self._h, _ptr(f), P, sigma, int(seed) & (2 ** 64 - 1), int(gen), _ptr(gd),
+                                        _ptr(grad), _ptr(st), _ptr(ws), self._stream()))
+        return grad, st
+
+    def debug_policy_image(self, set_to=None, out=None):
+        """The env's own packed policy image [7552] (a diagnostic); set_to: install that image instead."""
+        t = self.torch
+        if set_to is not None:
+            im = self._opt_tensor(set_to, (_abi.HG_POLICY_IMAGE_FLOATS,), "set_to", who="debug_policy_image")
+            self._check(self.lib.hg_debug_set_policy_image(self._h, _ptr(im), self._stream()))
+            return im
+        if out is None:
+            out = t.empty((_abi.HG_POLICY_IMAGE_FLOATS,), dtype=t.float32, device=self.device)
+        out = self._opt_tensor(out, (_abi.HG_POLICY_IMAGE_FLOATS,), "out", who="debug_policy_image")
+        self._check(self.lib.hg_debug_get_policy_image(self._h, _ptr(out), self._stream()))
+        return out
+
     # ------------------------------------------------------------------ branched planning rollouts
     def _plan_tensor(self, x, shape, name, dtype=None):
         """`x` as the library reads it: a contiguous tensor of `shape` and `dtype` on the env's device

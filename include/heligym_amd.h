@@ -906,6 +906,133 @@ int32_t hg_debug_philox(const uint32_t* in_dev, uint32_t* out_dev, int64_t count
  * after the first stamp.  Not part of the reference surface. */
 int32_t hg_clock_stamp(uint64_t* dst_dev, void* stream);
 
+/* ---- Populations of policies and an evolution-strategies learner on the device.
+ *
+ * A handle holds one policy image; the calls below run MANY policies over the envs of one handle in one
+ * launch and build the gradient-free learner (OpenAI-ES: antithetic pairs, centred ranks) around that
+ * rollout.  Every device call is asynchronous on `stream`, allocates nothing, makes no host decision that
+ * depends on device data and can be captured into a graph; none uses a floating-point atomic, and every launch
+ * shape is a function of the arguments and compile-time constants, so two calls on equal inputs give equal
+ * bits.  HG_E_INVALID means nothing was enqueued and no output was touched; the arguments that do not need
+ * the handle are checked before it, so they are refused with a NULL env too.
+ *
+ * theta is hg_ppo_grad's flat layout [HG_PPO_N_PARAMS].  An IMAGE is a packed policy as the rollout kernels
+ * load it (csrc/policy_mlp.h): hg_policy_image_floats() = 7552 floats.  A population's images are
+ * caller-owned device memory [P, 7552], 16-byte aligned. */
+int64_t hg_policy_image_floats(void);           /* 7552; host only */
+
+/* Image p (p = 0 .. P-1) = bitwise what hg_set_policy_theta(theta_dev + 5641 p, obs_mean_dev, obs_scale_dev)
+ * leaves in a handle's own buffer, the value head's elements included; with stochastic == 0 the head words
+ * (exp(log_std), the stochastic flag, the log_std sum) are those of hg_set_policy with log_std == NULL: zero.
+ * obs_mean_dev / obs_scale_dev [17] or NULL (0 / 1), shared by all members.  One launch for all P images.
+ * The env is used for its device and the error convention only.
+ * HG_E_INVALID: NULL env, theta_dev or images_dev; images_dev not 16-byte aligned, another pointer not
+ * 4-byte aligned; P outside 1 .. 65536. */
+int32_t hg_pop_pack(hg_env* env, const float* theta_dev, int64_t P, int32_t stochastic, const float* obs_mean_dev,
+                    const float* obs_scale_dev, float* images_dev, void* stream);
+
+/* hg_rollout_policy (eta_dev == NULL: in-kernel noise; injected noise is not offered) in which the wave of
+ * state tile t -- envs 64 t .. 64 t + 63 -- evaluates image (64 t) / envs_per_member of images_dev [P, 7552]:
+ * member p owns envs p * envs_per_member .. min(N, (p + 1) * envs_per_member) - 1.  Outputs, their stacking,
+ * restrictions (no auto-resets in HG_RESET_RETRIM), the action noise's key (an env's noise depends on its own
+ * counters, not on its member) and hg_debug_launches accounting (a lone-wave launch) are hg_rollout_policy's;
+ * member p's rows are bitwise hg_rollout_policy's of a handle of that member's envs with env_offset
+ * advanced by p * envs_per_member, the same seed and image p as its policy.  The handle's own policy is
+ * neither read nor required nor modified.
+ * HG_E_INVALID: what hg_rollout_policy refuses (its "no policy set" excepted); NULL or misaligned (16 bytes)
+ * images_dev; P outside 1 .. 65536; envs_per_member not a positive multiple of 64; N outside
+ * ((P - 1) * envs_per_member, P * envs_per_member] (every member owns at least one env; the last may be
+ * short or ragged). */
+int32_t hg_rollout_pop(hg_env* env, const float* images_dev, int64_t P, int64_t envs_per_member, const float* obs0_dev,
+                       int32_t nsteps, float* actions_out_dev, float* obs_dev, float* reward_dev,
+                       uint8_t* terminated_dev, uint8_t* truncated_dev, uint8_t* info_dev, void* stream);
+
+/* ES members from counters.  The noise of pair j (members 2 j and 2 j + 1), parameter i < 5572 (the
+ * actor-mean parameters W1 .. b3; log_std, w_v, b_v are not perturbed), generation
+ *   g = gen + (gen_dev ? *gen_dev : 0), a 64-bit sum; gen_dev [1] i32 is read when the kernel runs, so a
+ *       replayed graph whose gen_dev points at a counter (the optimiser state's `applied` or `seen` word)
+ *       draws fresh noise every replay:
+ *   eps_j[i] = normal (i & 3) of the four Box-Muller normals (z0 .. z3 of hg_set_policy's noise paragraph,
+ *              the same u(r), f(r), R0, R1) of ONE Philox4x32-10 call on
+ *   counter = (i >> 2, j, g_lo, g_hi),   key = (seed_lo ^ 0x65735F6E, seed_hi ^ 0x6F697365).
+ * The noise is never stored: hg_es_perturb and hg_es_grad both regenerate it.
+ *
+ * hg_es_perturb: theta_{2j} = fma(sigma, eps_j, theta), theta_{2j+1} = fma(-sigma, eps_j, theta) element-wise in
+ * fp32 for i < 5572, theta's own bits for i >= 5572; images_dev [P, 7552] image p = bitwise hg_pop_pack of
+ * theta_p (stochastic, obs_mean_dev, obs_scale_dev as there); member_theta_dev [P, 5641] or NULL receives the
+ * theta_p themselves (how a caller keeps the best member).  One launch; the noise goes from registers into
+ * the packed layout, and no [P, 5641] intermediate exists when member_theta_dev is NULL.
+ * HG_E_INVALID: NULL env, theta_dev or images_dev; images_dev not 16-byte aligned, another pointer not 4-byte;
+ * P odd or outside 2 .. 65536; sigma not finite or <= 0. */
+int32_t hg_es_perturb(hg_env* env, const float* theta_dev, int64_t P, float sigma, uint64_t seed, int64_t gen,
+                      const int32_t* gen_dev, int32_t stochastic, const float* obs_mean_dev, const float* obs_scale_dev,
+                      float* images_dev, float* member_theta_dev, void* stream);
+
+/* Diagnostic, the counterpart of hg_debug_eta: out_dev [5572] = eps_pair as the two calls around it compute
+ * it (the same device function).  HG_E_INVALID: NULL env or out_dev; a misaligned (4 bytes) pointer; pair
+ * outside 0 .. 32767. */
+int32_t hg_es_noise(hg_env* env, uint64_t seed, int64_t gen, const int32_t* gen_dev, int64_t pair, float* out_dev,
+                    void* stream);
+
+/* Per-member fitness from what hg_rollout_pop wrote, accumulated across calls (long episodes are collected
+ * in chunks of K steps).  reward_dev [K, N] fp32, terminated_dev / truncated_dev [K, N] u8 (N the env's),
+ * members as in hg_rollout_pop.
+ *   HG_POP_FIT_WINDOW:        every reward counts (the flags are not read and may be NULL).
+ *   HG_POP_FIT_FIRST_EPISODE: an env's rewards count up to and including its first step with
+ *                             terminated | truncated since the last restart; alive_dev [N] u8 (required)
+ *                             carries that across calls: 1 while the env still counts.
+ *   restart != 0: sum = 0 and alive = 1 are taken before this call's rewards, inside the same launch.
+ * Per env: e_n = an fp64 sum of its counted rewards over k ascending, from 0 (rewards are selected, not
+ * multiplied by a flag: nothing of a finished env's later rows enters).  Per member, with c = its env count
+ * (envs_per_member, less for the last): thread t (0 .. 255) adds e_n of its envs base + t, base + t + 256, ..
+ * in ascending order from 0; the 256 thread sums are added by the halving tree s[t] += s[t + w], w = 128, 64,
+ * .. 1 -- an order that depends on envs_per_member and c only.  Then sum_dev[p] += that (fp64) and
+ * fitness_out_dev[p] = (float)(sum_dev[p] / c): the mean counted reward sum per env of member p so far.
+ * (Every addition is fp64 on fp32 rewards: chunked calls and one call over the concatenation agree bitwise
+ * whenever no addition rounds -- e.g. a member's counted rewards spanning under 2^16 in magnitude and fewer
+ * than 2^13 of them -- and to fp64 rounding otherwise.)  A non-finite reward makes that member's sum and fitness non-finite and
+ * touches no other member.
+ * HG_E_INVALID: NULL env, reward_dev, sum_dev or fitness_out_dev; a mode outside the enum; FIRST_EPISODE
+ * without terminated_dev, truncated_dev or alive_dev; sum_dev not 8-byte or an fp32 pointer not 4-byte
+ * aligned; K < 1; P, envs_per_member, N as hg_rollout_pop refuses them. */
+enum { HG_POP_FIT_WINDOW = 0, HG_POP_FIT_FIRST_EPISODE = 1 };
+
+int32_t hg_pop_fitness(hg_env* env, const float* reward_dev, const uint8_t* terminated_dev, const uint8_t* truncated_dev,
+                       int32_t K, int64_t P, int64_t envs_per_member, int32_t mode, int32_t restart, uint8_t* alive_dev,
+                       double* sum_dev, float* fitness_out_dev, void* stream);
+
+/* The ES gradient estimate from P fitnesses, fitness_dev [P] fp32 (member order: pair j = members 2 j, 2 j + 1).
+ *   rank     r_p = #{q : f_q < f_p} + #{q < p : f_q == f_p}, where every non-finite f (NaN included) counts as
+ *            -inf (so they rank lowest, ties by index): r is always a permutation of 0 .. P-1.
+ *   utility  u_p = fl(r_p / (P - 1)) - 1/2 in fp32: one correctly rounded fp32 division, one subtraction.
+ *   grad[i]  = s * sum_j (u_{2j} - u_{2j+1}) eps_j[i] for i < 5572, exactly 0 for 5572 <= i < 5641, with
+ *            s = (float)(-1 / ((double)P * (double)sigma)) and eps regenerated from hg_es_perturb's counters
+ *            (seed, gen, gen_dev as there).  The minus sign makes hg_ppo_adam's descent ascend the fitness.
+ *   order    w_j = u_{2j} - u_{2j+1} (one fp32 subtraction); pairs in chunks of 16 consecutive ones; per chunk
+ *            acc = fma(w_j, eps_j[i], acc) over its pairs ascending, from 0; the chunks' sums added ascending,
+ *            from 0; one multiplication by s.  A function of P and compile-time constants only.
+ *   stats_dev [8] or NULL: [0] mean (an fp64 sum, rounded once), [1] min, [2] max of the finite fitnesses
+ *            (NaN when there is none)  [3] the number of non-finite ones  [4] the index of the best finite
+ *            member, the lowest index among ties (-1 when there is none)  [5] ||grad||_2 (fp32, hg_ppo_adam's
+ *            summation order)  [6], [7] zero.
+ * P is even, 2 .. 16384 (the ranks are P^2 comparisons); hg_es_workspace_bytes(P) bytes at workspace_dev,
+ * 16-byte aligned, contents irrelevant before and after (the utilities, then one partial gradient per
+ * chunk).  Three launches, a fourth with stats_dev.  grad_dev feeds hg_ppo_adam(theta, grad, NULL, state, cfg) unchanged: its
+ * non-finite guard, norm clip, Adam and lr_dev apply.  Z-score shaping and weight decay are not offered.
+ * HG_E_INVALID: NULL env, fitness_dev, grad_dev or workspace_dev; workspace_dev not 16-byte, another pointer
+ * not 4-byte aligned; P odd or outside 2 .. 16384; sigma not finite or <= 0.  hg_es_workspace_bytes returns
+ * HG_E_INVALID for such a P. */
+int64_t hg_es_workspace_bytes(int64_t P);       /* a multiple of 16; host only */
+
+int32_t hg_es_grad(hg_env* env, const float* fitness_dev, int64_t P, float sigma, uint64_t seed, int64_t gen,
+                   const int32_t* gen_dev, float* grad_dev, float* stats_dev, void* workspace_dev, void* stream);
+
+/* Diagnostics (tests): copy the handle's own packed policy image to image_out_dev [7552], or replace it with
+ * image_dev [7552] (any image of a population; the handle then counts as having a policy and a value
+ * head).  Device-to-device copies on `stream`. */
+int32_t hg_debug_get_policy_image(hg_env* env, float* image_out_dev, void* stream);
+int32_t hg_debug_set_policy_image(hg_env* env, const float* image_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
