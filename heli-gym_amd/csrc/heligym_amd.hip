@@ -32,6 +32,7 @@
 #include "es.h"
 #include "retrim_body.h"
 #include "baked.h"
+#include "weather.h"
 
 using hg::Params;
 using hg::Template;
@@ -420,6 +421,13 @@ struct BranchPolicyArgs {
     float value_scale = 1.f;
 };
 
+// hg_set_weather's per-env records (weather.h): a kernel argument of the weather kernels alone, after every
+// other one -- no existing kernel's argument segment moves.
+struct WeatherArgs {
+    const f32x4* rec = nullptr;    // [tiles][2][64] 16-byte words: {wm_n, wm_e, cos, sin}, {sigma_low, turb_level, 0, 0}
+    const float* tep = nullptr;    // [tiles * 64][16] the env's TEP row (13 values), read above 1000 ft only
+};
+
 // TASK: reward / success of the task; ETA: noise injected by the caller (else in-kernel Philox);
 // NT: streaming output stores (see st_out); FEAT: the optional features (reset-info compaction,
 // per-reset re-trim, next-step auto-reset, TimeLimit) -- without them the kernel carries none of
@@ -448,14 +456,20 @@ struct BranchPolicyArgs {
 // (hgp::residual_action).  One hgp::policy_eval(sample = false) per iteration gives that mean and V of the
 // same observation, which is the bootstrap term of a row the previous step truncated and, in one more
 // iteration that leaves before the step, of the rows that survived the horizon.
+// WEATHER (hg_set_weather; off in every kernel that existed before it): the wind model's weather constants --
+// mean wind, its direction's cos / sin, sigma_low, the TEP row -- are the lane's own, from wx's per-env
+// record, instead of the handle's (Params, or BAKED's literals).  The record's two words are requested with
+// the state groups, once per launch; the TEP row inside the wind model's branch for lanes above 1000 ft.
 template <int TASK, bool ETA, bool NT, bool FEAT, bool MULTI, bool BAKED, bool NTS, int HELP = 0, bool POLICY = false,
-          bool AC = false, bool BRANCH = false>
+          bool AC = false, bool BRANCH = false, bool WEATHER = false>
 __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p,
                                           ParamArg Pa, const Template<float>* __restrict__ Tp, const StepArgs& a,
                                           int64_t bid, const PolicyArgs& pol = PolicyArgs{}, const AcArgs& ac = AcArgs{},
                                           const BranchArgs& br = BranchArgs{},
-                                          const BranchPolicyArgs& bp = BranchPolicyArgs{}) {
+                                          const BranchPolicyArgs& bp = BranchPolicyArgs{},
+                                          const WeatherArgs& wx = WeatherArgs{}) {
     static_assert(HELP == 0 || (!ETA && !MULTI), "wind helper waves: in-kernel noise, one step per launch");
+    static_assert(!WEATHER || (HELP == 0 && !BRANCH && FEAT), "per-env weather: the one-wave step, per-env templates");
     static_assert(!POLICY || (MULTI && HELP == 0), "the in-kernel policy belongs to the rollout");
     static_assert(!AC || POLICY, "log-probabilities and values are the in-kernel policy's");
     static_assert(!BRANCH || (MULTI && FEAT && HELP == 0 && !AC), "branched rollouts: the rollout's steps");
@@ -570,6 +584,15 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
         hs[6] = g5.x; hs[7] = g5.y; hs[8] = g5.z; hs[9] = g5.w;
         hs[10] = g6.x; hs[11] = g6.y; hs[12] = g6.z; hs[13] = g6.w;
         hs[2] = 0.f; hs[3] = 0.f;
+    }
+    // WEATHER: the lane's record, requested behind the state groups (the rows are padded to whole tiles)
+    hg::LaneWind lw = {};
+    if constexpr (WEATHER) {
+        const f32x4* rec = wx.rec + tile * (2 * kTileEnvs);
+        const f32x4 r0 = ld_lane(rec, lt), r1 = ld_lane(rec + kTileEnvs, lt);
+        lw.wm[0] = r0.x; lw.wm[1] = r0.y; lw.wind_dir_cos = r0.z; lw.wind_dir_sin = r0.w;
+        lw.sigma_low = r1.x;
+        lw.tep_row = wx.tep + (blk0 + tid) * hgw::kTepFloats;
     }
 #ifndef HG_EARLY_PAIRS   // 1: the stages' constant pairs formed while the state loads are in flight (round 5
 #define HG_EARLY_PAIRS 0  // A/B: 7.062 -> 7.088 us, profiles/r05_valu_ab.txt; not adopted)
@@ -732,7 +755,8 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
 
     // ground height under the committed position (F6), wind step (Heli.step :195-199)
     TSTAMP(2, "v"(eta[2]), "v"(eta[0]));
-    hg::wind_step_f32<NT>(P, ws, carry, eta, W);   // (the lone-wave kernels: the uniform-branch form)
+    if constexpr (WEATHER) hg::wind_step_f32<NT>(P, lw, ws, carry, eta, W);
+    else hg::wind_step_f32<NT>(P, ws, carry, eta, W);   // (the lone-wave kernels: the uniform-branch form)
     TSTAMP(3, "v"(W[2]), "v"(W[0]));
     const hg::Ground<float> h_c = hg::ground_combine<float>(tex_c, cell_c);
 
@@ -1144,6 +1168,48 @@ __global__ __launch_bounds__(64, 1) void rollout_ac_kernel(float* __restrict__ s
                                                            const PolicyArgs pol, const AcArgs ac) {
     step_body<TASK, ETA, true, FEAT, true, BAKED, false, 0, true, true>(state_p, n_p, seed_p, envoff_p, Pa, Tp, a,
                                                                         blockIdx.x, pol, ac);
+}
+
+// Per-env weather (hg_set_weather): the step, the rollout and the two policy rollouts with step_body's
+// WEATHER, kernels of their own names beside the ones above, which stay as they were.  Always with the
+// optional features (per-env weather comes with per-env reset templates).  No helper-wave, non-temporal bulk
+// or run-time specialised variant: the variants are bitwise equal, so a weather handle runs fewer of them.
+// (hg_rollout_pop's is below; the branched rollouts refuse a weather handle.)
+template <int TASK, bool ETA, bool NT, bool MULTI, bool BAKED>
+__global__ __launch_bounds__(kStepBlock, NT ? HG_MIN_WAVES : HG_MIN_WAVES_BULK) void step_weather_kernel(
+    float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
+    const Template<float>* __restrict__ Tp, const StepArgs a, const WeatherArgs wx) {
+    step_body<TASK, ETA, NT, true, MULTI, BAKED, false, 0, false, false, false, true>(
+        state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, PolicyArgs{}, AcArgs{}, BranchArgs{}, BranchPolicyArgs{}, wx);
+}
+
+template <int TASK, bool ETA, bool BAKED>
+__global__ __launch_bounds__(64, 1) void rollout_policy_weather_kernel(
+    float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
+    const Template<float>* __restrict__ Tp, const StepArgs a, const PolicyArgs pol, const WeatherArgs wx) {
+    step_body<TASK, ETA, true, true, true, BAKED, false, 0, true, false, false, true>(
+        state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, pol, AcArgs{}, BranchArgs{}, BranchPolicyArgs{}, wx);
+}
+
+template <int TASK, bool ETA, bool BAKED>
+__global__ __launch_bounds__(64, 1) void rollout_ac_weather_kernel(
+    float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
+    const Template<float>* __restrict__ Tp, const StepArgs a, const PolicyArgs pol, const AcArgs ac,
+    const WeatherArgs wx) {
+    step_body<TASK, ETA, true, true, true, BAKED, false, 0, true, true, false, true>(
+        state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, pol, ac, BranchArgs{}, BranchPolicyArgs{}, wx);
+}
+
+// hg_rollout_pop on a weather handle: rollout_pop_kernel's member offset in front of the weather rollout
+template <int TASK, bool BAKED>
+__global__ __launch_bounds__(64, 1) void rollout_pop_weather_kernel(
+    float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
+    const Template<float>* __restrict__ Tp, const StepArgs a, const PolicyArgs pol, const uint32_t tiles_per_member,
+    const WeatherArgs wx) {
+    PolicyArgs mine = pol;
+    mine.pk = pol.pk + (size_t)(blockIdx.x / tiles_per_member) * hgp::kPolicyFloats;
+    step_body<TASK, false, true, true, true, BAKED, false, 0, true, false, false, true>(
+        state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, mine, AcArgs{}, BranchArgs{}, BranchPolicyArgs{}, wx);
 }
 
 // hg_rollout_branch: the rollout's steps on N * branches rows that start from the N envs' states
@@ -1801,7 +1867,7 @@ __global__ __launch_bounds__(kBlock) void philox_kernel(const uint32_t* in, uint
 
 // ------------------------------------------------------------------------------ host model
 
-constexpr double kD2R = 3.14159265358979323846 / 180.0;
+using hgw::kD2R;
 
 // First n at which the reference's float accumulator crosses its threshold
 // (helicopter.py:193 `time_counter += DT` vs `> max_time`; :205 `successed_time += DT` vs `>=`).
@@ -1919,17 +1985,8 @@ Params<R> derive(const hg_config& c, int rows, int cols) {
     P.ns_half = (R)(a.env_NS_MAX / 2);
     P.ew_half = (R)(a.env_EW_MAX / 2);
     // wind (wind_dynamics.py:21-28, 56)
-    const double wdir = a.env_WIND_DIR_deg * kD2R;
-    P.wm[0] = (R)(a.env_WIND_SPD * (double)(float)cos(wdir));
-    P.wm[1] = (R)(a.env_WIND_SPD * (double)(float)sin(wdir));
-    P.wm[2] = (R)0;
-    P.wind_dir_cos = (R)cos(wdir);
-    P.wind_dir_sin = (R)sin(wdir);
-    const double w20 = a.env_TURB_LVL / 7.0 * 88.61;
-    P.w20 = (R)w20;
-    P.sigma_low = (R)(0.1 * w20);
-    P.turb_level = (R)a.env_TURB_LVL;
-    hg::tep_row_values(P.turb_level, P.tep_row);
+    // (weather.h: the same function forms a per-env weather's record, hg_set_weather)
+    hgw::set_wind(P, hgw::wind_constants<R>(a.env_WIND_DIR_deg, a.env_WIND_SPD, (double)a.env_TURB_LVL));
     P.eta_norm = (R)(1.0 / sqrt(dt));
     // folded constants of the packed fp32 step (stage_f32.h), formed in double
     P.f_kc_irho = (R)(0.75 * mr_OM * a.mr_E / a.mr_R / gam_dro);
@@ -2141,6 +2198,11 @@ struct hg_env {
     int32_t* ov_ring = nullptr;             // [3] their counts
     float* tmpl_env = nullptr;              // per-env reset templates [N][39] (hg_set_reset_templates)
     bool env_templates = false;
+    // per-env weather (hg_set_weather): the records the weather kernels read (weather.h) and the host's copy
+    bool weather = false;
+    float* wx_rec = nullptr;                // [tiles][2][64] 16-byte words
+    float* wx_tep = nullptr;                // [tiles * 64][16]
+    std::vector<hg_weather> weather_host;   // [N] while set
     float* policy_dev = nullptr;            // the MLP policy's packed image (hg_set_policy, policy_mlp.h)
     bool policy_set = false;
     bool value_set = false;                 // hg_set_value_head was called
@@ -2300,8 +2362,29 @@ static void launch_step(const hg_env* e, hipStream_t s, const StepArgs& a) {
 // it; with or without the optional features.
 // (returns the run-time specialised launch's status; the library's own launches report through
 // hipGetLastError)
+#define WEATHER_ARG(e) WeatherArgs{reinterpret_cast<const f32x4*>((e)->wx_rec), (e)->wx_tep}
+// A weather handle's step or rollout: the lone-wave variant while the batch fits two waves per SIMD, the bulk
+// one past it; injected or in-kernel noise; the constant-specialised step when the env uses it.
+template <int T, bool MULTI>
+static void dispatch_step_weather(const hg_env* e, hipStream_t s, const StepArgs& a, bool eta) {
+    const unsigned grid = (unsigned)((e->n + kStepBlock - 1) / kStepBlock);
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kStepBlock), 0, s, STEP_KARGS(e), a, WEATHER_ARG(e)); };
+    auto pick = [&](auto nt) {
+        constexpr bool NT = decltype(nt)::value;
+        ++e->n_launch[NT ? 4 : 5];
+        if (e->baked) eta ? go(step_weather_kernel<T, true, NT, MULTI, true>) : go(step_weather_kernel<T, false, NT, MULTI, true>);
+        else eta ? go(step_weather_kernel<T, true, NT, MULTI, false>) : go(step_weather_kernel<T, false, NT, MULTI, false>);
+    };
+    if (e->n <= HG_NT_WAVES * e->resident_envs) pick(std::true_type{});
+    else pick(std::false_type{});
+}
+
 template <int T, bool MULTI>
 static hipError_t dispatch_step(const hg_env* e, hipStream_t s, const StepArgs& a, bool eta, bool feat) {
+    if (e->weather) {
+        dispatch_step_weather<T, MULTI>(e, s, a, eta);
+        return hipSuccess;
+    }
     if (!MULTI && !eta && e->rtc) {   // the airframe's run-time specialised kernels, same size rules
         const int v = e->n <= HG_NT_WAVES * e->resident_envs ? 0 : (e->n <= HG_NTS_WAVES * e->resident_envs ? 2 : 4);
         float* state = e->state;
@@ -2351,6 +2434,14 @@ static void launch_rollout_policy(const hg_env* e, hipStream_t s, const StepArgs
     const unsigned grid = (unsigned)((e->n + 63) / 64);
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, STEP_KARGS(e), a, pol); };
     ++e->n_launch[4];
+    if (e->weather) {
+        auto gw = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, STEP_KARGS(e), a, pol, WEATHER_ARG(e));
+        };
+        if (e->baked) eta ? gw(rollout_policy_weather_kernel<T, true, true>) : gw(rollout_policy_weather_kernel<T, false, true>);
+        else eta ? gw(rollout_policy_weather_kernel<T, true, false>) : gw(rollout_policy_weather_kernel<T, false, false>);
+        return;
+    }
     if (e->baked) {
         if (feat) eta ? go(rollout_policy_kernel<T, true, true, true>) : go(rollout_policy_kernel<T, false, true, true>);
         else eta ? go(rollout_policy_kernel<T, true, false, true>) : go(rollout_policy_kernel<T, false, false, true>);
@@ -2366,6 +2457,13 @@ static void launch_rollout_pop(const hg_env* e, hipStream_t s, const StepArgs& a
     const unsigned grid = (unsigned)((e->n + 63) / 64);
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, STEP_KARGS(e), a, pol, tiles); };
     ++e->n_launch[4];
+    if (e->weather) {
+        auto gw = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, STEP_KARGS(e), a, pol, tiles, WEATHER_ARG(e));
+        };
+        e->baked ? gw(rollout_pop_weather_kernel<T, true>) : gw(rollout_pop_weather_kernel<T, false>);
+        return;
+    }
     if (e->baked) feat ? go(rollout_pop_kernel<T, true, true>) : go(rollout_pop_kernel<T, false, true>);
     else feat ? go(rollout_pop_kernel<T, true, false>) : go(rollout_pop_kernel<T, false, false>);
 }
@@ -2384,6 +2482,14 @@ static void launch_rollout_ac(const hg_env* e, hipStream_t s, const StepArgs& a,
     const unsigned grid = (unsigned)((e->n + 63) / 64);
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, STEP_KARGS(e), a, pol, ac); };
     ++e->n_launch[4];
+    if (e->weather) {
+        auto gw = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, STEP_KARGS(e), a, pol, ac, WEATHER_ARG(e));
+        };
+        if (e->baked) eta ? gw(rollout_ac_weather_kernel<T, true, true>) : gw(rollout_ac_weather_kernel<T, false, true>);
+        else eta ? gw(rollout_ac_weather_kernel<T, true, false>) : gw(rollout_ac_weather_kernel<T, false, false>);
+        return;
+    }
     if (e->baked) {
         if (feat) eta ? go(rollout_ac_kernel<T, true, true, true>) : go(rollout_ac_kernel<T, false, true, true>);
         else eta ? go(rollout_ac_kernel<T, true, false, true>) : go(rollout_ac_kernel<T, false, false, true>);
@@ -2620,7 +2726,7 @@ static void release(hg_env* e) {
     dfree(e->hmap); dfree(e->state); dfree(e->az); dfree(e->tmpl_dev); dfree(e->params_dev);
     dfree(e->trim_block); dfree(e->retrim_wind); dfree(e->retrim_list); dfree(e->retrim_recs);
     dfree(e->ov_recs); dfree(e->ov_ring); dfree(e->fused_ring);
-    dfree(e->tmpl_env); dfree(e->setup_batch); dfree(e->policy_dev);
+    dfree(e->tmpl_env); dfree(e->setup_batch); dfree(e->policy_dev); dfree(e->wx_rec); dfree(e->wx_tep);
     delete e;
 }
 
@@ -2840,6 +2946,8 @@ int32_t hg_set_target(hg_env* e, const hg_target* t) {
 
 int32_t hg_set_trim_cond(hg_env* e, const hg_trim_cond* tc) {
     if (!e || !tc) return fail(HG_E_INVALID, "bad env or trim cond");
+    if (e->weather)
+        return fail(HG_E_INVALID, "hg_set_trim_cond: per-env weather is set; pass the conditions as `conds` to hg_set_weather");
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     const hg_trim_cond old = e->cfg.trim;
@@ -3845,6 +3953,7 @@ int32_t hg_rollout_branch(hg_env* e, const float* actions, int32_t horizon, int3
     if (!e) return fail(HG_E_INVALID, "env is NULL");
     int64_t rows = 0;
     if (branch_rows("hg_rollout_branch", e, branches, &rows) != HG_OK) return HG_E_INVALID;
+    if (e->weather) return fail(HG_E_INVALID, "hg_rollout_branch does not support per-env weather (hg_set_weather)");
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     StepArgs a;
@@ -3924,6 +4033,7 @@ int32_t hg_rollout_branch_policy(hg_env* e, const float* obs0, const float* resi
         return fail(HG_E_INVALID, "hg_rollout_branch_policy: bootstrap HG_BOOTSTRAP_VALUE needs a value head (hg_set_value_head)");
     int64_t rows = 0;
     if (branch_rows(who, e, branches, &rows) != HG_OK) return HG_E_INVALID;
+    if (e->weather) return fail(HG_E_INVALID, "hg_rollout_branch_policy does not support per-env weather (hg_set_weather)");
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     StepArgs a;
@@ -4023,6 +4133,10 @@ int32_t hg_mppi_value(hg_env* e, const float* ret, int32_t branches, float lambd
     return HG_OK;
 }
 
+static int32_t trim_conds_batch(hg_env* e, const hg_trim_cond* conds, int64_t count, const float* wind, float* state,
+                                float* action, float* obs, int32_t* status, hipStream_t s);
+static int32_t set_reset_templates(hg_env* e, const float* templates, void* stream);
+
 int32_t hg_trim_batch(hg_env* e, const float* wind, int64_t count, float* state, float* action, float* obs,
                       int32_t* status, void* stream) {
     if (!e) return fail(HG_E_INVALID, "env is NULL");
@@ -4053,6 +4167,12 @@ int32_t hg_trim_conds_batch(hg_env* e, const hg_trim_cond* conds, int64_t count,
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     if (count < 0 || (count > 0 && !conds)) return fail(HG_E_INVALID, "bad conds / count");
     if (count == 0) return HG_OK;
+    return trim_conds_batch(e, conds, count, wind, state, action, obs, status, (hipStream_t)stream);
+}
+
+// (the handle's device is current; also hg_set_weather's trims)
+static int32_t trim_conds_batch(hg_env* e, const hg_trim_cond* conds, int64_t count, const float* wind, float* state,
+                                float* action, float* obs, int32_t* status, hipStream_t s) {
     if (count > e->setup_batch_cap) {
         dfree(e->setup_batch);
         e->setup_batch = nullptr;
@@ -4067,7 +4187,6 @@ int32_t hg_trim_conds_batch(hg_env* e, const hg_trim_cond* conds, int64_t count,
         // another condition's Jacobian needs other pivots, and the solve searches)
         memcpy(host[j].piv, e->setup.piv, sizeof(host[j].piv));
     }
-    hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemcpyAsync(e->setup_batch, host.data(), sizeof(hg::TrimSetup) * count, hipMemcpyHostToDevice, s));
     hgk::RetrimArgs r;
     memset(&r, 0, sizeof(r));
@@ -4089,6 +4208,131 @@ int32_t hg_trim_conds_batch(hg_env* e, const hg_trim_cond* conds, int64_t count,
 
 int32_t hg_set_reset_templates(hg_env* e, const float* templates, void* stream) {
     if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (e->weather)
+        return fail(HG_E_INVALID, "hg_set_reset_templates: per-env weather is set; pass the conditions as `conds` to "
+                                  "hg_set_weather (NULL weather reverts)");
+    return set_reset_templates(e, templates, stream);
+}
+
+// Per-env weather.  Host work first (validation, records, trim setups), then the batched device trim against
+// each env's own mean wind; only when every trim converged is anything of the handle replaced.
+int32_t hg_set_weather(hg_env* e, const hg_weather* weather, const hg_trim_cond* conds, int32_t* status_dev, void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!weather) {   // back to the handle-wide weather and the shared template
+        if (!e->weather) return HG_OK;
+        e->weather = false;
+        e->weather_host.clear();
+        return set_reset_templates(e, nullptr, stream);
+    }
+    if (e->cfg.reset_mode == HG_RESET_RETRIM)
+        return fail(HG_E_INVALID, "hg_set_weather: per-env weather needs reset_mode HG_RESET_TEMPLATE (its resets are per-env "
+                                  "templates)");
+    std::vector<float> rec, tep, wind;
+    const char* why = nullptr;
+    const int64_t bad = hgw::build_records(weather, e->n, rec, tep, wind, &why);
+    if (bad >= 0) return fail(HG_E_INVALID, "hg_set_weather: env " + std::to_string(bad) + ": " + why);
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    const int64_t n = e->n;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<hg_trim_cond> shared;
+    if (!conds) {
+        shared.assign((size_t)n, e->cfg.trim);
+        conds = shared.data();
+    }
+    // scratch: winds [n,3] | trimmed states [n,18] | observations [n,17] | status [n]
+    float* scratch = nullptr;
+    HIP_TRY(hipMalloc(&scratch, sizeof(float) * (size_t)n * (3 + 18 + 17 + 1)));
+    float* d_wind = scratch;
+    float* d_state = d_wind + 3 * n;
+    float* d_obs = d_state + 18 * n;
+    int32_t* d_status = reinterpret_cast<int32_t*>(d_obs + 17 * n);
+    std::vector<float> h_state((size_t)n * 18), h_obs((size_t)n * 17);
+    std::vector<int32_t> h_status((size_t)n, HG_E_TRIM);
+    auto work = [&]() -> int32_t {
+        HIP_TRY(hipMemcpyAsync(d_status, h_status.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_wind, wind.data(), sizeof(float) * 3 * n, hipMemcpyHostToDevice, s));
+        const int32_t rc = trim_conds_batch(e, conds, n, d_wind, d_state, nullptr, d_obs, d_status, s);   // synchronises
+        if (rc != HG_OK) return rc;
+        HIP_TRY(hipMemcpy(h_status.data(), d_status, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+        int64_t nbad = 0, first = -1;
+        for (int64_t i = 0; i < n; ++i)
+            if (h_status[i] != HG_OK) {
+                if (first < 0) first = i;
+                ++nbad;
+            }
+        if (status_dev) HIP_TRY(hipMemcpy(status_dev, d_status, sizeof(int32_t) * n, hipMemcpyDeviceToDevice));
+        if (nbad)
+            return fail(HG_E_TRIM, "hg_set_weather: the trim of " + std::to_string(nbad) + " env(s) against their mean wind "
+                                   "failed (first: env " + std::to_string(first) + "); the handle is unchanged");
+        HIP_TRY(hipMemcpy(h_state.data(), d_state, sizeof(float) * 18 * n, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h_obs.data(), d_obs, sizeof(float) * 17 * n, hipMemcpyDeviceToHost));
+        return HG_OK;
+    };
+    const int32_t rc = work();
+    if (rc != HG_OK) {
+        dfree(scratch);
+        return rc;
+    }
+    // the templates: trimmed heli state 18 | carry 4 (obs N/E/D velocity, ground altitude) | observation 17
+    std::vector<float> tmpl((size_t)n * kTplFloats);
+    for (int64_t i = 0; i < n; ++i) {
+        float* t = &tmpl[(size_t)i * kTplFloats];
+        const float* o = &h_obs[(size_t)i * 17];
+        memcpy(t, &h_state[(size_t)i * 18], sizeof(float) * 18);
+        t[18] = o[4]; t[19] = o[5]; t[20] = o[6]; t[21] = o[16];
+        memcpy(t + 22, o, sizeof(float) * 17);
+    }
+    auto install = [&]() -> int32_t {
+        HIP_TRY(hipDeviceSynchronize());   // queued steps may still read the records being replaced
+        if (!e->wx_rec) HIP_TRY(hipMalloc(&e->wx_rec, sizeof(float) * rec.size()));
+        if (!e->wx_tep) HIP_TRY(hipMalloc(&e->wx_tep, sizeof(float) * tep.size()));
+        HIP_TRY(hipMemcpy(e->wx_rec, rec.data(), sizeof(float) * rec.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->wx_tep, tep.data(), sizeof(float) * tep.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(scratch, tmpl.data(), sizeof(float) * tmpl.size(), hipMemcpyHostToDevice));
+        return set_reset_templates(e, scratch, s);   // (scratch holds n * 39 floats: it was sized so)
+    };
+    const int32_t rc2 = install();
+    dfree(scratch);
+    if (rc2 != HG_OK) return rc2;
+    e->weather = true;
+    e->weather_host.assign(weather, weather + n);
+    return HG_OK;
+}
+
+int32_t hg_get_weather(hg_env* e, hg_weather* out_host, float* templates_dev, void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!out_host && !templates_dev) return fail(HG_E_INVALID, "hg_get_weather: nothing to return (both outputs NULL)");
+    if (out_host) {
+        const hg_airframe& a = e->cfg.af;
+        const hg_weather own = {(float)a.env_TURB_LVL, (float)a.env_WIND_DIR_deg, (float)a.env_WIND_SPD};
+        for (int64_t i = 0; i < e->n; ++i) out_host[i] = e->weather ? e->weather_host[(size_t)i] : own;
+    }
+    if (templates_dev) {
+        DevGuard dev_guard(e);
+        if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+        hipStream_t s = (hipStream_t)stream;
+        if (e->env_templates) {
+            HIP_TRY(hipMemcpyAsync(templates_dev, e->tmpl_env, sizeof(float) * kTplFloats * e->n, hipMemcpyDeviceToDevice, s));
+        } else {   // the shared template, one row per env
+            std::vector<float> rows((size_t)e->n * kTplFloats);
+            for (int64_t i = 0; i < e->n; ++i) memcpy(&rows[(size_t)i * kTplFloats], &e->tmpl, sizeof(float) * kTplFloats);
+            HIP_TRY(hipMemcpyAsync(templates_dev, rows.data(), sizeof(float) * rows.size(), hipMemcpyHostToDevice, s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return HG_OK;
+}
+
+int32_t hg_weather_constants(const hg_config* cfg, const hg_weather* w, float record[8], float tep_row[16]) {
+    if (!cfg || !w || !record || !tep_row) return fail(HG_E_INVALID, "hg_weather_constants: NULL argument");
+    const char* why = hgw::check_weather(*w);
+    if (why) return fail(HG_E_INVALID, std::string("hg_weather_constants: ") + why);
+    hgw::weather_record(*w, record, tep_row);
+    return HG_OK;
+}
+
+static int32_t set_reset_templates(hg_env* e, const float* templates, void* stream) {
     e->ov_chain = kChainBroken;   // the next step's pending resets take the serial re-trim
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");

@@ -380,6 +380,14 @@ struct WindPar {
     R cos_az, sin_az;
 };
 
+// A lane's own weather (per-env weather, hg_set_weather): the fields of Params the wind model reads, under
+// their names there, so that wind_params / wind_step take either.  tep_row points at the env's row of the
+// TEP table, read only above 1000 ft.
+struct LaneWind {
+    float wm[2], wind_dir_cos, wind_dir_sin, sigma_low;
+    const float* tep_row;
+};
+
 // lookup.py:146-183 (get_value_2D) on the 7x12 TEP table: row key = turbulence level, column
 // key = ground altitude; clamped linear interpolation, no extrapolation.
 // MIL-HDBK-1797 turbulence exceedance table as the reference fills its LookUpTable(7,12)
@@ -439,9 +447,11 @@ HD R tep_lookup(const R* __restrict__ row, R colKey) {
 // wave-uniform branch taken only when some lane is above 1000 ft -- the same values, one block
 // instead of a divergent if / else around the common case (65 536 envs: -0.07 us; the bulk variant
 // keeps the if / else)
-template <typename R, bool UNIFORM = false>
-HD WindPar<R> wind_params(const Params<R>& P, const R carry[4]) {
-    const R vx = carry[0] + P.wm[0], vy = carry[1] + P.wm[1], vz = carry[2] + P.wm[2];
+// K: where the weather's constants come from -- the handle's own (Params, the two-argument form below) or a
+// lane's own (LaneWind: per-env weather); wm[2] is 0 in every weather and stays the handle's.
+template <typename R, bool UNIFORM = false, typename WK = Params<R>>
+HD WindPar<R> wind_params(const Params<R>& P, const WK& K, const R carry[4]) {
+    const R vx = carry[0] + K.wm[0], vy = carry[1] + K.wm[1], vz = carry[2] + P.wm[2];
     const R vel = m_sqrt(vx * vx + vy * vy + vz * vz);
     const R h = carry[3];
     R Lu, Lv, Lw, s_u, s_v, s_w, ca, sa;
@@ -451,26 +461,26 @@ HD WindPar<R> wind_params(const Params<R>& P, const R carry[4]) {
         Lu = hl * m_exp2((R)-1.2 * lb);
         Lv = (R)0.5 * Lu;
         Lw = (R)0.5 * hl;
-        s_w = P.sigma_low;
+        s_w = K.sigma_low;
         s_u = s_w * m_exp2((R)-0.4 * lb);
         s_v = s_u;
-        ca = P.wind_dir_cos;
-        sa = P.wind_dir_sin;
+        ca = K.wind_dir_cos;
+        sa = K.wind_dir_sin;
     };
     auto mid_high_alt = [&]() {
         R ax, ay;
         if (h >= (R)2000) {                   // high altitude
             Lu = (R)1750; Lv = (R)875; Lw = (R)875;
-            s_u = tep_lookup(P.tep_row, h);
+            s_u = tep_lookup(K.tep_row, h);
             ax = vx; ay = vy;
         } else {                              // medium: blend of the two (QUIRK: Lw = Lu, :76)
             const R r = (h - (R)1000) * (R)0.001;
             Lu = (R)1000 + r * (R)750;
             Lv = (R)0.5 * Lu;
             Lw = Lu;
-            s_u = P.sigma_low + r * (tep_lookup(P.tep_row, h) - P.sigma_low);
-            ax = vx * r + P.wm[0] * ((R)1 - r);
-            ay = vy * r + P.wm[1] * ((R)1 - r);
+            s_u = K.sigma_low + r * (tep_lookup(K.tep_row, h) - K.sigma_low);
+            ax = vx * r + K.wm[0] * ((R)1 - r);
+            ay = vy * r + K.wm[1] * ((R)1 - r);
         }
         s_v = s_u; s_w = s_u;
         // cos/sin of atan2(ay, ax) without the transcendental (atan2(0,0) = 0)
@@ -504,6 +514,10 @@ HD WindPar<R> wind_params(const Params<R>& P, const R carry[4]) {
     w.sin_az = sa;
     return w;
 }
+template <typename R, bool UNIFORM = false>
+HD WindPar<R> wind_params(const Params<R>& P, const R carry[4]) {
+    return wind_params<R, UNIFORM>(P, P, carry);
+}
 
 // wind_dynamics.py:101-109
 template <typename R>
@@ -518,10 +532,10 @@ HD void wind_f(const WindPar<R>& w, const R eta[3], const R s[5], R d[5]) {
 // WindDynamics.step (dynamics.py:158-171 + wind_dynamics.py:85-125).  QUIRK: the
 // derivative object is aliased across the RK stages, so the update is s += dt * k4; the stage
 // inputs are still formed from k1..k3.  Wind output from the stage-4 input state.
-template <typename R>
-HD void wind_step(const Params<R>& P, R s[5], const R carry[4], const R eta[3],
+template <typename R, typename WK = Params<R>>
+HD void wind_step(const Params<R>& P, const WK& K, R s[5], const R carry[4], const R eta[3],
                   R W[3]) {
-    const WindPar<R> w = wind_params(P, carry);
+    const WindPar<R> w = wind_params<R, false>(P, K, carry);
     R k[5], st[5];
     wind_f(w, eta, s, k);
 #pragma unroll
@@ -536,11 +550,15 @@ HD void wind_step(const Params<R>& P, R s[5], const R carry[4], const R eta[3],
     const R ut = w.K_u * st[0];
     const R vt = w.K_v * (st[2] + (R)(2 * kSqrt3) * st[1]);
     const R wt = w.K_w * (st[4] + (R)(2 * kSqrt3) * st[3]);
-    W[0] = P.wm[0] + (w.cos_az * ut - w.sin_az * vt);
-    W[1] = P.wm[1] + (w.sin_az * ut + w.cos_az * vt);
+    W[0] = K.wm[0] + (w.cos_az * ut - w.sin_az * vt);
+    W[1] = K.wm[1] + (w.sin_az * ut + w.cos_az * vt);
     W[2] = P.wm[2] + wt;
 #pragma unroll
     for (int i = 0; i < 5; ++i) s[i] = s[i] + P.dt * k[i];
+}
+template <typename R>
+HD void wind_step(const Params<R>& P, R s[5], const R carry[4], const R eta[3], R W[3]) {
+    wind_step(P, P, s, carry, eta, W);
 }
 
 // ------------------------------------------------------------------------------------------

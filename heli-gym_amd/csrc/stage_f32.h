@@ -204,9 +204,11 @@ HD StepK step_k(const Params<float>& P) {
 // Q = (vs0, ws0), R = (vs1, ws1); u is the first-order filter.  QUIRK: the update is
 // s += dt k4, the stage inputs still formed from k1..k3; the wind output from the stage-4 input.
 // Same operations per component as physics.h wind_step, so the same roundings.
-template <bool UNIFORM = false>
-HD void wind_step_f32(const Params<float>& P, float s[5], const float carry[4], const float eta[3], float W[3]) {
-    const WindPar<float> w = wind_params<float, UNIFORM>(P, carry);
+// K: the weather's constants, the handle's (the form without it) or the lane's own (physics.h wind_params)
+template <bool UNIFORM = false, typename WK = Params<float>>
+HD void wind_step_f32(const Params<float>& P, const WK& K, float s[5], const float carry[4], const float eta[3],
+                      float W[3]) {
+    const WindPar<float> w = wind_params<float, UNIFORM>(P, K, carry);
     const f2 A = f2{w.a_v, w.a_w}, B = f2{w.b_v, w.b_w}, E = f2{eta[1], eta[2]};
     const float U = s[0];
     const f2 Q = f2{s[1], s[3]}, R = f2{s[2], s[4]};
@@ -229,14 +231,18 @@ HD void wind_step_f32(const Params<float>& P, float s[5], const float carry[4], 
     // output at the stage-4 input (wind_dynamics.py:111-123)
     const float ut = w.K_u * U3;
     const f2 vw = f2{w.K_v, w.K_w} * (R3 + (float)(2 * kSqrt3) * Q3);
-    W[0] = P.wm[0] + (w.cos_az * ut - w.sin_az * vw.x);
-    W[1] = P.wm[1] + (w.sin_az * ut + w.cos_az * vw.x);
+    W[0] = K.wm[0] + (w.cos_az * ut - w.sin_az * vw.x);
+    W[1] = K.wm[1] + (w.sin_az * ut + w.cos_az * vw.x);
     W[2] = P.wm[2] + vw.y;
     // update with k4 only (F3)
     s[0] = U + dt * kU;
     const f2 Qn = Q + dt * kQ, Rn = R + dt * Q3;
     s[1] = Qn.x; s[3] = Qn.y;
     s[2] = Rn.x; s[4] = Rn.y;
+}
+template <bool UNIFORM = false>
+HD void wind_step_f32(const Params<float>& P, float s[5], const float carry[4], const float eta[3], float W[3]) {
+    wind_step_f32<UNIFORM>(P, P, s, carry, eta, W);
 }
 
 // (sin, cos) of the three attitude angles

@@ -88,6 +88,10 @@ class hg_trim_result(ctypes.Structure):
                 ("failed", ctypes.c_int32)]
 
 
+class hg_weather(ctypes.Structure):
+    _fields_ = [("turb_level", ctypes.c_float), ("wind_dir_deg", ctypes.c_float), ("wind_spd", ctypes.c_float)]
+
+
 class hg_ppo_opt_cfg(ctypes.Structure):
     _fields_ = [("lr", ctypes.c_double), ("lr_dev", ctypes.c_void_p), ("beta1", ctypes.c_double),
                 ("beta2", ctypes.c_double), ("eps", ctypes.c_double), ("max_grad_norm", ctypes.c_float),
@@ -197,6 +201,10 @@ _SIGS = {
     "hg_trim_conds_batch": (ctypes.c_int32, [_P, ctypes.POINTER(hg_trim_cond), ctypes.c_int64, _P, _P, _P, _P,
                                              _P, _P]),
     "hg_set_reset_templates": (ctypes.c_int32, [_P, _P, _P]),
+    "hg_set_weather": (ctypes.c_int32, [_P, ctypes.POINTER(hg_weather), ctypes.POINTER(hg_trim_cond), _P, _P]),
+    "hg_get_weather": (ctypes.c_int32, [_P, ctypes.POINTER(hg_weather), _P, _P]),
+    "hg_weather_constants": (ctypes.c_int32, [ctypes.POINTER(hg_config), ctypes.POINTER(hg_weather),
+                                              ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "hg_debug_params": (ctypes.c_int32, [ctypes.POINTER(hg_config), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                          _P, ctypes.c_int64]),
     "hg_config_is_baked": (ctypes.c_int32, [ctypes.POINTER(hg_config), ctypes.c_int32, ctypes.c_int32]),

@@ -1516,6 +1516,57 @@ class HeliVecEnv(*_VEC_BASES):
         self._check(self.lib.hg_set_reset_templates(self._h, _ptr(tmpl), self._stream()))
         return r
 
+    def set_weather(self, turb_level=None, wind_dir=None, wind_spd=None, conds=None):
+        """Per-env weather (hg_set_weather): turbulence level (0 .. 7, may be fractional), mean wind direction
+        (degrees) and speed (ft/s), each a scalar or an [N] array; a missing key takes the airframe document's
+        ENV value.  Every env is trimmed on the device against its own mean wind -- for `conds`, a list of N
+        trim-condition dicts, or the env's shared condition -- and resets to that trim from now on.  Returns
+        the trims as set_trim_conds does (state, obs, status; device tensors), `templates` included.  With no
+        argument: back to the handle-wide weather and the shared template (returns None).  Raises
+        HeliGymError naming the first envs whose trim failed; the env is then as it was.
+        reset_mode="template" only.  Synchronises; call it outside graph capture, step inside as before."""
+        t, N = self.torch, self.num_envs
+        if turb_level is None and wind_dir is None and wind_spd is None and conds is None:
+            self._check(self.lib.hg_set_weather(self._h, None, None, None, self._stream()))
+            return None
+        af = self.cfg.af
+        cols = []
+        for v, own, name in ((turb_level, af.env_TURB_LVL, "turb_level"), (wind_dir, af.env_WIND_DIR_deg, "wind_dir"),
+                             (wind_spd, af.env_WIND_SPD, "wind_spd")):
+            a = np.asarray(own if v is None else (v.detach().cpu().numpy() if hasattr(v, "detach") else v), dtype=np.float32)
+            if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != N):
+                raise ValueError(f"set_weather: {name} must be a scalar or have {N} entries, got shape {a.shape}")
+            cols.append(np.broadcast_to(a, (N,)))
+        arr = (_abi.hg_weather * N)()
+        np.frombuffer(arr, dtype=np.float32).reshape(N, 3)[:] = np.stack(cols, axis=1)
+        carr = None
+        if conds is not None:
+            if len(conds) != N:
+                raise ValueError(f"need {N} trim conditions, got {len(conds)}")
+            carr = (_abi.hg_trim_cond * N)()
+            for j, c in enumerate(conds):
+                config.fill_trim(carr[j], c)
+        status = t.full((N,), -99, dtype=t.int32, device=self.device)
+        rc = self.lib.hg_set_weather(self._h, arr, carr, _ptr(status), self._stream())
+        if rc == -3:   # HG_E_TRIM: name the envs
+            bad = (status != 0).nonzero().flatten()
+            raise _abi.HeliGymError(f"heligym_amd error {rc}: trim failed for envs {bad[:10].tolist()} "
+                                    f"({len(bad)} of {N}); the weather was not set")
+        self._check(rc)
+        tm = self.get_weather()["templates"]
+        return {"state": tm[:, :_abi.HG_N_HELI], "obs": tm[:, 22:], "status": status, "templates": tm}
+
+    def get_weather(self):
+        """dict of [N] float32 arrays turb_level, wind_dir, wind_spd (the airframe's values while no per-env
+        weather is set) and `templates`, the [N,39] device tensor of reset templates in use (state 18 | carry 4
+        | observation 17)."""
+        t, N = self.torch, self.num_envs
+        arr = (_abi.hg_weather * N)()
+        tm = t.empty((N, 39), dtype=t.float32, device=self.device)
+        self._check(self.lib.hg_get_weather(self._h, arr, _ptr(tm), self._stream()))
+        w = np.frombuffer(arr, dtype=np.float32).reshape(N, 3).copy()
+        return {"turb_level": w[:, 0], "wind_dir": w[:, 1], "wind_spd": w[:, 2], "templates": tm}
+
     def retrim_failures(self):
         """Auto-resets in reset_mode="retrim" whose trim did not converge (they got the template)."""
         c = ctypes.c_int64()
@@ -1563,3 +1614,21 @@ class HeliVecEnv(*_VEC_BASES):
         self._check(self.lib.hg_random_actions(self._h, _ptr(out), int(seed), int(step), float(lo),
                                                float(hi), self._stream()))
         return out
+
+
+def sample_weather(n, turb_level=(0.0, 7.0), wind_spd=(0.0, 40.0), wind_dir=(0.0, 360.0), seed=0):
+    """Uniform draws of n weathers for HeliVecEnv.set_weather(**sample_weather(n, ...)): a dict of [n] float32
+    arrays turb_level, wind_spd, wind_dir, each inside its closed (lo, hi) range, a function of `seed` alone
+    (NumPy's PCG64).  A range may also be one number (every env the same)."""
+    rng = np.random.default_rng(seed)
+    out = {}
+    for name, r in (("turb_level", turb_level), ("wind_spd", wind_spd), ("wind_dir", wind_dir)):
+        lo, hi = (r, r) if np.isscalar(r) else r
+        lo, hi = float(lo), float(hi)
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
+            raise ValueError(f"sample_weather: {name} range must be finite with lo <= hi, got {r}")
+        v = (lo + (hi - lo) * rng.random(int(n))).astype(np.float32)
+        # (the fp32 rounding may step over an end that is not an fp32 number)
+        v = np.where(v > hi, np.nextafter(v, np.float32(-np.inf)), v)
+        out[name] = np.where(v < lo, np.nextafter(v, np.float32(np.inf)), v).astype(np.float32)
+    return out

@@ -819,6 +819,47 @@ int32_t hg_trim_conds_batch(hg_env* env, const hg_trim_cond* conds, int64_t coun
  * template.  Copied; HG_RESET_TEMPLATE mode only. */
 int32_t hg_set_reset_templates(hg_env* env, const float* templates_dev, void* stream);
 
+/* ---- Per-env weather: turbulence level, mean wind direction and speed that differ across one handle's envs.
+ *
+ * The airframe document's ENV block (TURB_LVL, WIND_DIR, WIND_SPD) is the handle-wide weather.  A weather is
+ * the same three numbers for one env; turb_level may be fractional (the TEP table is interpolated as for the
+ * integer levels).  An env given a weather steps bitwise like an env of a handle whose airframe document has
+ * that ENV block (same seed, global env id and reset template). */
+typedef struct hg_weather {
+    float turb_level;     /* 0 .. 7 */
+    float wind_dir_deg;   /* the mean wind's direction, degrees */
+    float wind_spd;       /* ft/s, >= 0 */
+} hg_weather;
+
+/* weather [N] (host), or NULL: back to the handle-wide weather and the shared reset template.
+ * conds   [N] (host) trim conditions, or NULL: the handle's own for every env.
+ * Builds each env's constants (hg_weather_constants), trims every env on the device against its own mean
+ * wind (the code behind hg_trim_conds_batch) and installs the results as per-env reset templates (the code
+ * behind hg_set_reset_templates); env states are not touched (hg_reset starts episodes from the templates).
+ * status_dev [N] i32 or NULL receives each trim's status.  If any trim fails: HG_E_TRIM, and the handle is as
+ * it was.  HG_E_INVALID: a NULL env; a non-finite value, turb_level outside [0, 7] or wind_spd < 0 (the
+ * message names the first such env); reset_mode HG_RESET_RETRIM.
+ * Synchronises with the device; not capturable.  The stepping calls that follow are capturable as before:
+ * hg_step, hg_step_rows, hg_step_chained, hg_rollout, hg_rollout_policy, hg_rollout_ac and hg_rollout_pop
+ * honour the weather at every N (through kernels of their own: the lone-wave and the bulk step; no
+ * helper-wave, non-temporal bulk or run-time specialised variant, which are bitwise equal anyway).
+ * hg_rollout_branch and hg_rollout_branch_policy return HG_E_INVALID ("... per-env weather") while it is set; so do
+ * hg_set_trim_cond and hg_set_reset_templates (pass `conds` here instead).  hg_set_target, hg_set_max_time,
+ * hg_reset, hg_get_state and hg_set_state work as before. */
+int32_t hg_set_weather(hg_env* env, const hg_weather* weather, const hg_trim_cond* conds, int32_t* status_dev,
+                       void* stream);
+
+/* out_host [N] or NULL: each env's weather (the handle-wide one while none is set).  templates_dev [N,39]
+ * or NULL: the reset templates in use, hg_set_reset_templates' layout (the shared one in every row while no
+ * per-env templates are set).  Synchronises with `stream`. */
+int32_t hg_get_weather(hg_env* env, hg_weather* out_host, float* templates_dev, void* stream);
+
+/* Host only, no device: what hg_set_weather uploads for one env, formed by the code that forms the
+ * handle-wide constants from the ENV block.  record = {wm north, wm east, cos dir, sin dir, sigma_low,
+ * turb_level, 0, 0}; tep_row = the TEP table's row at turb_level (13 values) and 3 zeros.  `cfg` is
+ * validated for NULL only (no constant of a weather depends on the rest of the configuration today). */
+int32_t hg_weather_constants(const hg_config* cfg, const hg_weather* w, float record[8], float tep_row[16]);
+
 /* Run-time specialisation for airframes other than the compiled-in default one (whose constants
  * are instruction literals of the library's step kernel): load a gfx950 code object built from
  * csrc/step_rtc.hip with this env's constant image (`image`, the sizeof(Params<float>) bytes
