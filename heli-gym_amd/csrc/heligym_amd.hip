@@ -33,12 +33,9 @@
 #include "retrim_body.h"
 #include "baked.h"
 #include "weather.h"
+#include "step_kernels.h"
 
-using hg::Params;
-using hg::Template;
 using hgk::kCtrCol0;
-using hgk::kTileEnvs;
-using hgk::kTileWords;
 using hgk::tix;
 using hgk::AzRec;
 
@@ -63,1071 +60,12 @@ int32_t fail(int32_t code, const std::string& msg) {
     } while (0)
 
 constexpr int kBlock = 256;
-#ifndef HG_STEP_BLOCK
-#define HG_STEP_BLOCK 64
-#endif
-using hgk::kFusedLine;
-using hgk::kFusedSlot;
-using hgk::kFusedWaveCtrs;
-constexpr int kStepBlock = HG_STEP_BLOCK;   // step kernel block: one or more waves, one state tile each
-static_assert(kTileEnvs == 64, "a state tile is one wave");
 constexpr int kStateCols = HG_STATE_COLS;
 constexpr int kCtrCols = HG_COUNTER_COLS;
 
-
-// ------------------------------------------------------------------------------ Philox4x32-10
-struct U4 {
-    uint32_t x, y, z, w;
-};
-
-#ifndef HG_PHILOX_ROUNDS   // (A/B builds only: the library's noise stream is Philox4x32-10)
-#define HG_PHILOX_ROUNDS 10
-#endif
-__device__ __forceinline__ U4 philox(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int i = 0; i < HG_PHILOX_ROUNDS; ++i) {
-        const uint32_t lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
-        const uint32_t lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
-#ifndef HG_NO_BITOP3
-        // hi ^ y ^ k as one three-input bitwise instruction (truth table 0x96 = XOR3)
-        c = U4{(uint32_t)__builtin_amdgcn_bitop3_b32(hi1, c.y, k0, 0x96), lo1,
-               (uint32_t)__builtin_amdgcn_bitop3_b32(hi0, c.w, k1, 0x96), lo0};
-#else
-        c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-#endif
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
-
-// ((x >> 8) + 0.5) 2^-24 in fp32: from 2^23 on the + 0.5 rounds to even, so u is in (0, 1] (1 at the top:
-// a zero Box-Muller radius, never a log of 0); tests/philox_ref.py restates it bitwise
-__device__ __forceinline__ float u01(uint32_t x) {
-    return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f);
-}
-
 // ------------------------------------------------------------------------------ kernels
+// (the step itself -- StepArgs, step_body, step_kernel, step_help_kernel -- is step_kernels.h)
 
-// Kernel arguments.  What the state loads wait for -- the state base, n (a lane is active), the noise
-// key -- are the step kernel's first scalar parameters, preloaded into SGPRs at wave launch
-// (-amdgpu-kernarg-preload-count), so no scalar-load round trip sits in front of the state loads;
-// StepArgs follows, its feature-only fields last.  192 bytes in all, three scalar-cache lines (200
-// bytes, a fourth line on the critical path, cost 0.23 us per step).
-constexpr int kStepPreloadArgs = 6;   // state, n, seed, env_offset, Pa, Tp
-struct StepArgs {
-    const float2* hmap;
-    const float* actions;
-    float* obs;
-    float* reward;
-    uint8_t* terminated;
-    uint8_t* truncated;
-    uint8_t* info;
-    const float* eta;
-    float* final_obs_rows;       // [N,17] terminal observations of this step's auto-resets at their rows (hg_step_rows), or NULL
-    int32_t nsteps;          // MULTI: steps per launch (inputs / outputs stacked [nsteps][N])
-    int32_t retrim_slot;     // -1, or the slot of retrim_count's ring of three this step counts into (it
-                             // zeroes the next one)
-    // FEAT only
-    int32_t* reset_count;
-    int32_t* reset_count_next;   // zeroed by this launch for a later step (hg_step_chained), or NULL
-    int32_t* reset_index;
-    float* final_obs;
-    float* retrim_wind;      // reset_mode RETRIM: [3][N] wind of the step (the trim wind of a reset)
-    int4* retrim_recs;       // ... compacted jobs {env, trim wind} of the envs to re-trim
-    int32_t* retrim_count;   // ... their number: retrim_count[max(retrim_slot, 0)]
-    const float* tmpl_env;   // per-env reset templates [N][39] (Params::env_templates), else unused
-    // next-step auto-resets re-trimmed concurrently with the following step (reset_mode RETRIM):
-    int4* ov_recs;           // jobs {env, trim wind} of the envs whose episode ends this step, or NULL
-    int32_t* ov_count;       // ... their number (zeroed by the previous step of the sequence)
-    int32_t* ov_count_next;  // ... the next step's count, zeroed by this launch
-    int32_t ov_active;       // the resets due this step are being trimmed by a concurrent retrim_kernel
-                             // (ov mode): their state, but for the step counter, and their observation
-                             // rows are that kernel's to write
-    // fused same-step re-trim (step_fused_kernel): records published by device-coherent stores (env
-    // last), the resets deferred as in ov mode (the trim writes all but the step counter)
-    unsigned long long* fused_ctr;   // this launch's fused slot (kFusedSlot ints), or NULL (not fused)
-    int32_t* fused_next;     // the next launch's slot, zeroed by this launch
-};
-
-// Model constants travel as a pointer to a device copy (scalar loads); by value they would take
-// ~0.6 KB of kernel arguments and spill more SGPRs.
-using ParamArg = const Params<float>* __restrict__;
-
-#ifndef HG_NTS_WAVES   // bulk per-step launches store non-temporally up to this many waves per SIMD
-#define HG_NTS_WAVES 4
-#endif
-#ifndef HG_NT_WAVES   // the lone-wave (NT) variant up to this many waves per SIMD
-#define HG_NT_WAVES 2
-#endif
-#ifndef HG_MIN_WAVES
-#define HG_MIN_WAVES 1
-#endif
-#ifndef HG_EARLY_POST   // post-step terrain texels requested right after the RK update (0: after the reward)
-#define HG_EARLY_POST 1
-#endif
-#ifndef HG_MIN_WAVES_BULK   // launches with more waves than SIMDs (not NT): waves per SIMD the
-#define HG_MIN_WAVES_BULK 3   // registers must fit (3: <= 168 VGPRs; uncapped the bulk variant took
-#endif                        // 173 and ran two: 262 144 envs 21.1 -> 19.3 us, 1 M and 4 M unchanged)
-
-constexpr int kTplFloats = (int)(sizeof(Template<float>) / sizeof(float));
-static_assert(kTplFloats <= 64, "reset template must fit one float per lane");
-// the template's device copy holds one float per lane of a wave (HG_TPL_FULL: every lane loads one)
-constexpr size_t kTplAlloc = 64 * sizeof(float);
-#ifndef HG_RT_QUEUE_LATE   // the re-trim queue's records written after the state stores (lone-wave kernels)
-#define HG_RT_QUEUE_LATE 1
-#endif
-#ifndef HG_TPL_FULL_HELP
-#define HG_TPL_FULL_HELP 1
-#endif
-__device__ __forceinline__ float lane_value(float v, int lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
-// Output stores.  NT = non-temporal for the dword-and-wider columns (the byte flags stay plain):
-// used when the whole batch is resident at once (<= one wave per SIMD), where the step is latency
-// bound and streaming the outputs shortens the end-of-kernel write-back; with more waves than
-// SIMDs the plain write-back path is faster.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-template <bool NT, typename T>
-__device__ __forceinline__ void st_out(T* p, T v) {
-    if constexpr (NT && sizeof(T) >= 4) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
-template <bool NT>
-__device__ __forceinline__ void st_out4(float* p, const float* s) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(s);
-    if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
-    else *reinterpret_cast<f32x4*>(p) = v;
-}
-
-typedef __attribute__((address_space(4))) const Params<float> ConstParams;
-__device__ __forceinline__ const Params<float>* reload_params(const Params<float>* p) {
-    ConstParams* c = (ConstParams*)p;
-    asm volatile("" : "+s"(c));   // opaque: the loads cannot be hoisted out of the step loop
-    return (const Params<float>*)c;
-}
-
-// Per-lane access at a small byte offset from a uniform base (SGPR-base global load / store).  The
-// explicit global address space keeps the saddr form (`global_store_dword voff, v, s[base]`) even
-// for bases that went through an opaque copy, which would otherwise be flat stores with a 64-bit
-// VALU address add each.
-#define HG_GLOBAL __attribute__((address_space(1)))
-template <typename T>
-__device__ __forceinline__ T ld_lane(const T* __restrict__ base, uint32_t idx) {
-    const HG_GLOBAL char* g = (const HG_GLOBAL char*)base + idx * (uint32_t)sizeof(T);
-    if constexpr (sizeof(T) == 16) {   // float4: load as a plain vector (no address-space copy ctor)
-        typedef float v4 __attribute__((ext_vector_type(4)));
-        return __builtin_bit_cast(T, *(const HG_GLOBAL v4*)g);
-    } else {
-        return *(const HG_GLOBAL T*)g;
-    }
-}
-template <bool NT, typename T>
-__device__ __forceinline__ void st_lane(T* base, uint32_t idx, T v) {
-    HG_GLOBAL T* p = (HG_GLOBAL T*)((HG_GLOBAL char*)base + idx * (uint32_t)sizeof(T));
-    if constexpr (NT && sizeof(T) >= 4) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
-
-// Observations of a step: each wave stages its 64 rows in its own LDS slice (stride 17 is
-// bank-conflict free) and writes them back as contiguous float4, with no block-wide barrier.
-// MULTI (hg_rollout): step s's rows start at obs + s*N*17 floats, 16-byte aligned only when
-// N % 4 == 0 (or s % 4 == 0); unaligned rows go out as dwords.
-// `skip` (uniform): rows another kernel writes (the concurrently re-trimmed resets), stored around.
-template <bool NT, bool MULTI>
-__device__ __forceinline__ void store_obs_wave(float* w_obs, const float obs[17], float* dst, int64_t so, int64_t w0,
-                                               int64_t n, int lane, uint64_t skip = 0) {
-#pragma unroll
-    for (int c = 0; c < 17; ++c) w_obs[lane * 17 + c] = obs[c];
-    __builtin_amdgcn_wave_barrier();
-    const int nw = (n - w0) < 64 ? (int)(n - w0) : 64;
-    const int cnt = nw > 0 ? nw * 17 : 0;
-    float* out = dst + (so + w0) * 17;
-    if (skip) {
-        for (int j = lane; j < cnt; j += 64)
-            if (!((skip >> (j / 17)) & 1)) st_out<NT>(out + j, w_obs[j]);
-        return;
-    }
-    const bool aligned = !MULTI || (((uintptr_t)out & 15) == 0);
-    if (nw == 64 && aligned) {   // full wave: 272 float4, all LDS reads issued before the first store
-        f32x4 v[5];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) v[t] = *reinterpret_cast<const f32x4*>(w_obs + 4 * (lane + 64 * t));
-        if (lane < 16) v[4] = *reinterpret_cast<const f32x4*>(w_obs + 4 * (lane + 256));
-#pragma unroll
-        for (int t = 0; t < 4; ++t) st_out4<NT>(out + 4 * (lane + 64 * t), reinterpret_cast<const float*>(&v[t]));
-        if (lane < 16) st_out4<NT>(out + 4 * (lane + 256), reinterpret_cast<const float*>(&v[4]));
-        return;
-    }
-    const int n4 = aligned ? cnt >> 2 : 0;
-    for (int j = lane; j < n4; j += 64) st_out4<NT>(out + 4 * j, w_obs + 4 * j);
-    for (int j = (n4 << 2) + lane; j < cnt; j += 64) st_out<NT>(out + j, w_obs[j]);
-}
-
-
-// x in [-pi, pi) (fp32 pi rounds up, so the strict bounds are the fp32 values in [-pi, pi)); NaN: false
-__device__ __forceinline__ bool in_pi_range(float x) {
-    return x > -3.14159274101257324f && x < 3.14159274101257324f;
-}
-
-// RK4 combinations (dynamics.py:158-171) on pairs of state components, so that they issue as packed
-// fp32 (v_pk_fma_f32: two lanes' worth of fma per instruction at the issue cost of one): each
-// component is rounded exactly as the scalar `acc += 2k; st = hs + k h` / `hs += (acc + k) dt/6`.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-template <bool FIRST>
-__device__ __forceinline__ void rk_stage(const float* hs, const float* k, float* acc, float* st, float h) {
-#pragma unroll
-    for (int c = 0; c < 18; c += 2) {
-        const f32x2 kk = {k[c], k[c + 1]}, hh = {hs[c], hs[c + 1]};
-        f32x2 aa;
-        if (FIRST) {
-            aa = kk;
-        } else {
-            const f32x2 a0 = {acc[c], acc[c + 1]};
-            aa = a0 + 2.f * kk;
-        }
-        const f32x2 ss = hh + kk * h;
-        acc[c] = aa.x; acc[c + 1] = aa.y;
-        st[c] = ss.x; st[c + 1] = ss.y;
-    }
-}
-
-__device__ __forceinline__ void rk_update(float* hs, const float* k, const float* acc, float dt6) {
-#pragma unroll
-    for (int c = 0; c < 18; c += 2) {
-        const f32x2 kk = {k[c], k[c + 1]}, hh = {hs[c], hs[c + 1]}, aa = {acc[c], acc[c + 1]};
-        const f32x2 r = hh + (aa + kk) * dt6;
-        hs[c] = r.x; hs[c + 1] = r.y;
-    }
-}
-
-// Turbulence noise of a step (wind_dynamics.py:49-52: eta = randn(3) / sqrt(dt)): injected by the
-// caller (ETA), or Box-Muller normals from Philox4x32-10 keyed by (global env id, step, episode).
-template <bool ETA>
-__device__ __forceinline__ void draw_eta(const StepArgs& a, uint64_t seed, int64_t env_offset, const Params<float>& P,
-                                         int64_t so, int64_t blk0,
-                                         uint32_t lo, int32_t step, int32_t epi, float eta[3]) {
-    if (ETA) {
-        const float* eb = a.eta + 3 * (so + blk0);
-        eta[0] = ld_lane(eb + 0, 3 * lo);
-        eta[1] = ld_lane(eb + 1, 3 * lo);
-        eta[2] = ld_lane(eb + 2, 3 * lo);
-    } else {
-        const uint64_t gid = (uint64_t)(env_offset + blk0 + lo);
-        const U4 r = philox(U4{(uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)step, (uint32_t)epi},
-                            (uint32_t)seed, (uint32_t)(seed >> 32));
-        // Box-Muller.  Radii sqrt(-2 ln u) / sqrt(dt) = sqrt(log2(u) * (-2 ln 2 / dt)) with u in (0, 1]
-        // from the top 24 bits; angles in revolutions for the hardware sin / cos (v_sin_f32 takes
-        // revolutions: sin(2 pi u) = v_sin(u)), u in [1, 2) from the top 23 bits (a whole turn apart)
-        const float rk = P.eta_norm * P.eta_norm * -1.38629436111989061f;   // -2 ln 2 / dt
-        const float r0 = sqrtf(__log2f(u01(r.x)) * rk);
-        const float r1 = sqrtf(__log2f(u01(r.z)) * rk);
-        const float a1 = __uint_as_float((r.y >> 9) | 0x3f800000u), a3 = __uint_as_float((r.w >> 9) | 0x3f800000u);
-        eta[0] = r0 * __builtin_amdgcn_cosf(a1);
-        eta[1] = r0 * __builtin_amdgcn_sinf(a1);
-        eta[2] = r1 * __builtin_amdgcn_cosf(a3);
-    }
-}
-
-// Diagnostic build only: per-wave phase timestamps (s_memtime) of one launch, for latency
-// attribution; lane 0 of each of the first HG_TIMING_WAVES waves records them.
-#ifndef HG_TIMING
-#define HG_TIMING 0
-#endif
-
-#if HG_TIMING
-#define HG_TIMING_WAVES 2048
-#define HG_TIMING_SLOTS 17   // 0..13 phase stamps, 14/15 realtime end/start, 16 the wave's branch flags
-__device__ unsigned long long g_timing[HG_TIMING_WAVES][HG_TIMING_SLOTS];
-#define TSTAMP(j, ...)                                                                          \
-    do {                                                                                        \
-        asm volatile("" ::__VA_ARGS__);                                                         \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();                             \
-        const int w_ = (int)(i >> 6);                                                           \
-        if ((tid & 63) == 0 && w_ < HG_TIMING_WAVES) g_timing[w_][j] = t_;                      \
-    } while (0)
-// the stamping wave's tile from the hardware ids (the small-batch kernel's blocks are a stepping wave and
-// its helper: the stepping wave is wave 0, its tile the block).  A 128-thread block is taken for the
-// small-batch kernel's, so the timing build keeps the one-wave step blocks of the default build.
-static_assert(HG_STEP_BLOCK != 128, "HG_TIMING builds tell the helper kernel's blocks by their 128 threads");
-#define HG_STAMP_WAVE() (blockDim.x == 128 ? (int)blockIdx.x : (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6))
-// the same stamp from inside the RK driver (stage_f32.h), where only the hardware ids are in scope
-#define HG_STAGE_STAMP(j, ...)                                                                  \
-    do {                                                                                        \
-        asm volatile("" ::__VA_ARGS__);                                                         \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();                             \
-        const int w_ = HG_STAMP_WAVE();                                                         \
-        if ((threadIdx.x & 63) == 0 && w_ < HG_TIMING_WAVES) g_timing[w_][j] = t_;              \
-    } while (0)
-// which wave-uniform branches the wave took (HG_TIMING builds): 1 reset, 2 gear contact code,
-// 4 the full sincos of a large attitude increment
-#define HG_STAGE_FLAG(bit)                                                                      \
-    do {                                                                                        \
-        const int w_ = HG_STAMP_WAVE();                                                         \
-        if ((threadIdx.x & 63) == 0 && w_ < HG_TIMING_WAVES) g_timing[w_][16] |= (bit);         \
-    } while (0)
-// the small-batch kernel's helper waves (one per tile): 0 start (s_memrealtime), 1 start (s_memtime),
-// 2 the tile's counters arrived (noise key), 3 noise and wind step done, 4 past the hand-off barrier
-__device__ unsigned long long g_timing_help[HG_TIMING_WAVES][5];
-#define HSTAMP(j, ...)                                                                          \
-    do {                                                                                        \
-        asm volatile("" ::__VA_ARGS__);                                                         \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();                             \
-        if (lane == 0 && tile < HG_TIMING_WAVES) g_timing_help[tile][j] = t_;                   \
-    } while (0)
-#else
-#define TSTAMP(j, ...) do { } while (0)
-#define HSTAMP(j, ...) do { } while (0)
-#endif
-
-}  // namespace
-#include "stage_f32.h"   // (after the timing macros: HG_STAGE_STAMP)
-#include "policy_mlp.h"  // (after philox / u01)
-namespace {
-
-// hg_rollout_policy's arguments beside StepArgs (which keeps its size: the per-step kernels' argument
-// segment is three scalar-cache lines)
-struct PolicyArgs {
-    const float* pk = nullptr;     // the handle's packed policy (policy_mlp.h)
-    const float* obs0 = nullptr;   // [N,17] the observations step 0's actions are computed from
-    float* actions_out = nullptr;  // [nsteps,N,4] the sampled actions
-};
-
-// hg_rollout_ac's further outputs, [nsteps,N] each, any of them null (value and next_value together).
-// A struct of its own: PolicyArgs is a kernel argument of hg_rollout_policy's kernels.
-struct AcArgs {
-    float* logp = nullptr;         // log pi(a_k | o_k)
-    float* value = nullptr;        // V(o_k), o_k the observation a_k was computed from
-    float* next_value = nullptr;   // terminated[k] ? 0 : V(o'_k), o'_k step k's observation before any reset
-};
-
-// hg_rollout_branch's arguments beside StepArgs (of which it reads hmap, actions and nsteps); the kernel's
-// row count N * branches travels as its `n`.  A struct of its own, like the two above.
-struct BranchArgs {
-    float* ret = nullptr;              // [N*branches] discounted return of each row
-    int32_t* alive_steps = nullptr;    // [N*branches] steps up to and including the row's ending step, or NULL
-    uint8_t* end_info = nullptr;       // [N*branches] the ending step's HG_INFO_* bits (0: survived), or NULL
-    uint32_t branches = 1;             // rows per env: row r is branch r % branches of env r / branches
-    float gamma = 1.f;
-};
-
-// hg_rollout_branch_policy's arguments beside StepArgs, PolicyArgs (pk, obs0) and BranchArgs; all wave-uniform.
-// A struct of its own once more: no existing kernel's argument segment moves.
-struct BranchPolicyArgs {
-    const float* residual = nullptr;   // [nsteps, N*branches, 4] added to the policy's mean, or NULL
-    hgp::ActBox box = {};              // the applied action's bounds
-    int32_t bootstrap = 0;             // HG_BOOTSTRAP_VALUE: survivors and truncated rows add disc * value_scale * V(o')
-    float value_scale = 1.f;
-};
-
-// hg_set_weather's per-env records (weather.h): a kernel argument of the weather kernels alone, after every
-// other one -- no existing kernel's argument segment moves.
-struct WeatherArgs {
-    const f32x4* rec = nullptr;    // [tiles][2][64] 16-byte words: {wm_n, wm_e, cos, sin}, {sigma_low, turb_level, 0, 0}
-    const float* tep = nullptr;    // [tiles * 64][16] the env's TEP row (13 values), read above 1000 ft only
-};
-
-// TASK: reward / success of the task; ETA: noise injected by the caller (else in-kernel Philox);
-// NT: streaming output stores (see st_out); FEAT: the optional features (reset-info compaction,
-// per-reset re-trim, next-step auto-reset, TimeLimit) -- without them the kernel carries none of
-// their registers; MULTI: a.nsteps consecutive steps per launch (hg_rollout) with the env state
-// kept in registers between them; BAKED: the default airframe's model constants compiled in as
-// instruction literals (baked.h), the runtime fields still read from the device copy.  All
-// compile-time, so the hot kernel has no data-independent branches to merge around.
-// POLICY (with MULTI: hg_rollout_policy): each step's action is the handle's MLP policy
-// (policy_mlp.h) of the observation row the previous step wrote -- the lane's `obs` registers, from
-// `pol.obs0` at the first step -- and is stored to pol.actions_out; a.actions is not read.
-// The body is a device function so that the run-time specialised code objects (step_rtc.hip) wrap
-// the same code in kernels of their own names.
-// AC (with POLICY: hg_rollout_ac): the policy is evaluated by hgp::policy_eval, which also gives the
-// action's log-probability and the value head's V of the same observation, stored to ac.logp and
-// ac.value.  ac.next_value[k] is the value of the observation step k produced before any reset: where
-// step k did not reset, that is the next iteration's V, stored one step late (the last step's by one
-// more forward pass after the steps); where it reset, the terminal observation is about to be
-// overwritten and is evaluated at once, in a wave-uniform branch only waves with such a lane take.
-// BRANCH (with MULTI and FEAT: hg_rollout_branch): a lane is a row of the N * branches candidates
-// (n_p their number), `branches` consecutive rows start from one env's state, which each lane loads
-// from that env's tile slot and nobody writes back.  A row is stepped as above up to its first ending
-// step and never reset; nothing is stored per step, the discounted return, the step count and the
-// ending step's info bits once at the end.  ETA here means no noise (eta = 0), not injected noise.
-// BRANCH with POLICY (hg_rollout_branch_policy): the row's action is the policy's mean of the row's own
-// observation -- its env's row of pol.obs0 at the first step -- plus bp.residual's row, clamped
-// (hgp::residual_action).  One hgp::policy_eval(sample = false) per iteration gives that mean and V of the
-// same observation, which is the bootstrap term of a row the previous step truncated and, in one more
-// iteration that leaves before the step, of the rows that survived the horizon.
-// WEATHER (hg_set_weather; off in every kernel that existed before it): the wind model's weather constants --
-// mean wind, its direction's cos / sin, sigma_low, the TEP row -- are the lane's own, from wx's per-env
-// record, instead of the handle's (Params, or BAKED's literals).  The record's two words are requested with
-// the state groups, once per launch; the TEP row inside the wind model's branch for lanes above 1000 ft.
-template <int TASK, bool ETA, bool NT, bool FEAT, bool MULTI, bool BAKED, bool NTS, int HELP = 0, bool POLICY = false,
-          bool AC = false, bool BRANCH = false, bool WEATHER = false>
-__device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p,
-                                          ParamArg Pa, const Template<float>* __restrict__ Tp, const StepArgs& a,
-                                          int64_t bid, const PolicyArgs& pol = PolicyArgs{}, const AcArgs& ac = AcArgs{},
-                                          const BranchArgs& br = BranchArgs{},
-                                          const BranchPolicyArgs& bp = BranchPolicyArgs{},
-                                          const WeatherArgs& wx = WeatherArgs{}) {
-    static_assert(HELP == 0 || (!ETA && !MULTI), "wind helper waves: in-kernel noise, one step per launch");
-    static_assert(!WEATHER || (HELP == 0 && !BRANCH && FEAT), "per-env weather: the one-wave step, per-env templates");
-    static_assert(!POLICY || (MULTI && HELP == 0), "the in-kernel policy belongs to the rollout");
-    static_assert(!AC || POLICY, "log-probabilities and values are the in-kernel policy's");
-    static_assert(!BRANCH || (MULTI && FEAT && HELP == 0 && !AC), "branched rollouts: the rollout's steps");
-    static_assert(!(BRANCH && POLICY) || NT, "policy-guided branches: one wave per SIMD, the lone-wave step");
-    // the policy's matrix products take the wave's 64 envs as their columns: a block is one wave
-    static_assert(!POLICY || kStepBlock == 64, "hg_rollout_policy needs one-wave step blocks (HG_STEP_BLOCK 64)");
-    __shared__ float s_obs[(HELP ? HELP * 64 : kStepBlock) * HG_N_OBS];   // one 64-row slice per wave
-    __shared__ float s_wind[HELP ? HELP * 8 * 64 : 1];   // HELP: each tile's wind output and wind state
-    constexpr bool kNTS = NT || NTS;   // non-temporal output stores
-    const Params<float>& P0 = *Pa;   // model constants: scalar loads from a device copy
-    // BAKED: the default airframe's constants as instruction literals (baked.h); only the runtime
-    // fields (dt, target, limits, flags) are loaded
-    Params<float> PB;
-    if constexpr (BAKED) PB = hg::bake(*Pa);
-    const int lane = threadIdx.x & 63;
-    // HELP: blocks of HELP tiles, waves 0 .. HELP-1 step them, waves HELP .. 2 HELP-1 run their noise and
-    // wind step (helper wave j + HELP for tile j) and hand it over in LDS
-    const int wave_id = (kStepBlock == 64 && HELP == 0) ? 0 : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wv = HELP ? wave_id % (HELP ? HELP : 1) : wave_id;   // uniform
-    const int64_t tile = bid * (HELP ? HELP : kStepBlock / 64) + wv;
-    const int64_t blk0 = tile * 64;   // this wave's first env
-    const int tid = lane;
-    const int64_t i = blk0 + tid;
-    const int64_t n = n_p;
-    const bool active = i < n;
-    // Addressing: this wave's state tile (7 groups x 64 lanes x 16 bytes, contiguous, retrim.h) from
-    // one uniform (SGPR) base at group 4, so every group is an immediate offset (-4 .. +2 KB, inside
-    // the 13-bit field) of the same SGPR-base access with the lane's byte offset: no address
-    // arithmetic per group.  Lanes past the end of a ragged last tile step its padding and store
-    // nothing; for the caller's [N]-row buffers they read row blk0.
-    const uint32_t lo = (uint32_t)(active ? tid : 0);
-    const uint32_t lt = (uint32_t)tid;
-    f32x4* st_b = reinterpret_cast<f32x4*>(state_p + tile * kTileWords) + 4 * kTileEnvs;
-#define GRP(ptr, g) ((ptr) + ((g) - 4) * kTileEnvs)
-
-#if HG_TIMING
-    if ((tid & 63) == 0 && (i >> 6) < HG_TIMING_WAVES) {
-        g_timing[i >> 6][15] = __builtin_amdgcn_s_memrealtime();
-        g_timing[i >> 6][16] = 0;
-    }
-#endif
-    if constexpr (HELP > 0) {
-        const bool helper = wave_id >= HELP;
-        if (tile * 64 >= n_p) {   // (a last block's missing tiles: both waves meet at the barrier)
-            asm volatile("s_barrier" ::: "memory");
-            return;
-        }
-        if (helper) {   // the tile's noise and wind step (Heli.step :195-199), the same code as below
-#if HG_TIMING
-            if (lane == 0 && tile < HG_TIMING_WAVES) g_timing_help[tile][0] = __builtin_amdgcn_s_memrealtime();
-#endif
-            HSTAMP(1, "v"(lane));
-            const Params<float>& PH = BAKED ? PB : P0;
-            const f32x4 g0 = ld_lane(GRP(st_b, 0), lt), g1 = ld_lane(GRP(st_b, 1), lt), g2 = ld_lane(GRP(st_b, 2), lt),
-                        g3 = ld_lane(GRP(st_b, 3), lt);
-            float ws[5], carry[4], eta[3], W[3];
-            carry[3] = g1.z; carry[0] = g1.w; carry[1] = g2.x; carry[2] = g2.y;
-            ws[0] = g2.z; ws[1] = g2.w; ws[2] = g3.x; ws[3] = g3.y; ws[4] = g3.z;
-            HSTAMP(2, "v"(g0.w), "v"(g1.x));
-            draw_eta<false>(a, seed_p, envoff_p, PH, 0, blk0, lo, __float_as_int(g0.w), __float_as_int(g1.x), eta);
-            hg::wind_step_f32<true>(PH, ws, carry, eta, W);
-            HSTAMP(3, "v"(W[0]), "v"(ws[4]));
-            float* sw = s_wind + wv * 8 * 64 + lane;
-            sw[0] = W[0]; sw[64] = W[1]; sw[128] = W[2];
-#pragma unroll
-            for (int c = 0; c < 5; ++c) sw[(3 + c) * 64] = ws[c];
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            HSTAMP(4, "v"(lane));
-            return;
-        }
-    }
-    TSTAMP(0, "v"(tid));
-    // reset template (heli[18] | carry[4] | obs[17]) one float per lane, requested with the state so
-    // that a reset costs no round trip at the end (and no late load is outstanding when the step
-    // ends: a load issued near the stage-4 code makes the compiler wait for it there)
-    // the helper kernel: every lane loads (the device copy is padded to one float per lane, kTplAlloc),
-    // no divergent load (4 096 envs 5.20 -> 5.15 us; the other kernels measured slower so)
-    // (BRANCH: never a reset, no template)
-    const float tpl = BRANCH ? 0.f
-                             : ((HELP > 0 && HG_TPL_FULL_HELP) || lane < kTplFloats ? reinterpret_cast<const float*>(Tp)[lane] : 0.f);
-    // BRANCH: the env this lane's row branches from (rows past the end take row blk0's), and its state
-    // groups where its tile keeps them: per-lane 16-byte loads, up to 64 lanes of one address
-    uint32_t b_env = 0;
-    const f32x4* b_st = nullptr;
-    if constexpr (BRANCH) {
-        b_env = (uint32_t)(blk0 + lo) / br.branches;   // (rows < 2^31: checked by the host)
-        b_st = reinterpret_cast<const f32x4*>(state_p + (int64_t)(b_env / kTileEnvs) * kTileWords) + b_env % kTileEnvs;
-    }
-    // The state groups in the order they are needed (retrim.h slot table): position and step
-    // counter (-> terrain texel address, noise key), the rest of the key and the carry, the wind
-    // state (-> wind step), then the heli state.  hs[2], hs[3] (the rotor azimuths) are not stepped.
-    float hs[18], ws[5], carry[4];
-    int32_t step, succ, epi;
-    {
-        // (HELP: group 2 -- carry[1..2], wind state -- is the helper wave's; the carry is rewritten
-        // at the end of every step and the wind state comes back from the helper)
-        f32x4 g0, g1, g2, g3, g4, g5, g6;
-        if constexpr (BRANCH) {
-            g0 = b_st[0 * kTileEnvs]; g1 = b_st[1 * kTileEnvs]; g2 = b_st[2 * kTileEnvs]; g3 = b_st[3 * kTileEnvs];
-            g4 = b_st[4 * kTileEnvs]; g5 = b_st[5 * kTileEnvs]; g6 = b_st[6 * kTileEnvs];
-        } else {
-            g0 = ld_lane(GRP(st_b, 0), lt); g1 = ld_lane(GRP(st_b, 1), lt);
-            g2 = HELP ? f32x4{0.f, 0.f, 0.f, 0.f} : ld_lane(GRP(st_b, 2), lt);
-            g3 = ld_lane(GRP(st_b, 3), lt); g4 = ld_lane(GRP(st_b, 4), lt); g5 = ld_lane(GRP(st_b, 5), lt);
-            g6 = ld_lane(GRP(st_b, 6), lt);
-        }
-        hs[15] = g0.x; hs[16] = g0.y; hs[17] = g0.z; step = __float_as_int(g0.w);
-        epi = __float_as_int(g1.x); succ = __float_as_int(g1.y); carry[3] = g1.z; carry[0] = g1.w;
-        carry[1] = g2.x; carry[2] = g2.y; ws[0] = g2.z; ws[1] = g2.w;
-        ws[2] = g3.x; ws[3] = g3.y; ws[4] = g3.z; hs[14] = g3.w;
-        hs[0] = g4.x; hs[1] = g4.y; hs[4] = g4.z; hs[5] = g4.w;
-        hs[6] = g5.x; hs[7] = g5.y; hs[8] = g5.z; hs[9] = g5.w;
-        hs[10] = g6.x; hs[11] = g6.y; hs[12] = g6.z; hs[13] = g6.w;
-        hs[2] = 0.f; hs[3] = 0.f;
-    }
-    // WEATHER: the lane's record, requested behind the state groups (the rows are padded to whole tiles)
-    hg::LaneWind lw = {};
-    if constexpr (WEATHER) {
-        const f32x4* rec = wx.rec + tile * (2 * kTileEnvs);
-        const f32x4 r0 = ld_lane(rec, lt), r1 = ld_lane(rec + kTileEnvs, lt);
-        lw.wm[0] = r0.x; lw.wm[1] = r0.y; lw.wind_dir_cos = r0.z; lw.wind_dir_sin = r0.w;
-        lw.sigma_low = r1.x;
-        lw.tep_row = wx.tep + (blk0 + tid) * hgw::kTepFloats;
-    }
-#ifndef HG_EARLY_PAIRS   // 1: the stages' constant pairs formed while the state loads are in flight (round 5
-#define HG_EARLY_PAIRS 0  // A/B: 7.062 -> 7.088 us, profiles/r05_valu_ab.txt; not adopted)
-#endif
-#if HG_EARLY_PAIRS
-    // (data-independent: issued ahead of the first wait for the state, off the step's critical path)
-    const hg::StepK Kpairs = hg::step_k<NT && HG_PIN_CONSTANTS>(BAKED ? PB : P0);
-#endif
-    if (FEAT && !BRANCH && bid == 0 && tid == 0) {   // counters of a later step (rings of three)
-        if (a.reset_count_next) *a.reset_count_next = 0;
-        if (a.retrim_slot >= 0 && a.retrim_count) a.retrim_count[a.retrim_slot == 2 ? 0 : a.retrim_slot + 1] = 0;
-        if (a.ov_count_next) *a.ov_count_next = 0;
-    }
-    if (FEAT && !BRANCH && bid == 0 && a.fused_next && tid < kFusedWaveCtrs + 1) a.fused_next[kFusedLine * tid] = 0;
-    if (FEAT && !BRANCH && bid == 0 && a.fused_next && tid < 2) a.fused_next[1 + tid] = 0;
-    const int nsteps = MULTI ? a.nsteps : 1;
-    // BRANCH: the row's return and discount, its steps so far, its ending step's info bits; a row is
-    // alive until its first ending step.  The rows of an env waiting for its next-step reset (whose next
-    // step ignores the action) are over before they start.
-    float br_G = 0.f, br_disc = 1.f;
-    int32_t br_T = 0;
-    uint32_t br_end = 0;
-    bool br_alive = BRANCH && active && !(P0.autoreset_next && step < 0);
-    bool defer_st = false;   // (one step per launch) a deferred reset: the step counter alone is stored
-    // the re-trim queue (below): the wave's job mask, the slot counter's old value (leader lane), this
-    // lane's job and its trim wind
-    unsigned long long rt_mask = 0;
-    int rt_base = 0;
-    bool rt_job = false, rt_next = false;
-    // (the bulk variant writes them at once: the values kept live past the stores cost it registers,
-    // 262 144 envs 46.6 -> 47.3 us with the late write)
-    constexpr bool kRtLate = HG_RT_QUEUE_LATE && NT && !MULTI;
-    unsigned long long rc_mask = 0;   // the same for the compacted reset info
-    int rc_base = 0;
-    bool rc_job = false;
-    float fo[kRtLate ? 17 : 1];
-    float rw0 = 0.f, rw1 = 0.f, rw2 = 0.f;
-    auto rt_queue = [&]() {
-        if (FEAT && rt_mask) {
-            const int leader = __ffsll((long long)rt_mask) - 1;
-            const int slot = __builtin_amdgcn_readlane(rt_base, leader) + __popcll(rt_mask & ((1ull << lane) - 1ull));
-            if (rt_job && slot < n) {
-                if (rt_next) {   // a next-step reset: the wind recorded at the episode's last step
-                    rw0 = a.retrim_wind[i];
-                    rw1 = a.retrim_wind[n + i];
-                    rw2 = a.retrim_wind[2 * n + i];
-                }
-                if (a.fused_ctr) {
-                    // fused: the wind, then env, as device-coherent (agent-scope) stores with a wait for
-                    // the wind's between them -- the trim polls env and then reads the wind the same
-                    // way.  No release: the trim reads nothing else this wave stored (deferred reset),
-                    // so no L2 write-back is needed, and its waits for the record flush no cache.
-                    int* rp = reinterpret_cast<int*>(a.retrim_recs + slot);
-                    __hip_atomic_store(rp + 1, __float_as_int(rw0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(rp + 2, __float_as_int(rw1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(rp + 3, __float_as_int(rw2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __hip_atomic_store(rp, (int)i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                } else {
-                    a.retrim_recs[slot] = make_int4((int32_t)i, __float_as_int(rw0), __float_as_int(rw1), __float_as_int(rw2));
-                }
-            }
-        }
-    };
-    // POLICY: the weights as this lane's matrix operands, kept across the steps, and the observation
-    // row the next action is computed from (lanes past the end of a ragged tile read row blk0)
-    hgp::Weights pw;
-    float pobs[POLICY ? 17 : 1];
-    if constexpr (POLICY) {
-        hgp::load_weights(pol.pk, lane, pw);
-        // (BRANCH: the row's env's observation, as its state groups above)
-        const float* row = pol.obs0 + (BRANCH ? (int64_t)b_env : blk0 + lo) * 17;
-#pragma unroll
-        for (int c = 0; c < 17; ++c) pobs[c] = row[c];
-    }
-    // AC: whether the previous step reset the lane (its next_value is stored already) or terminated it
-    bool ac_prev_reset = false, ac_prev_term = false;
-    // (AC with values: one more pass after the last step, which only evaluates the last observation)
-    // (BRANCH with POLICY and a bootstrap: the same, for the survivors' V(o_H))
-    const int niter = AC ? nsteps + (ac.next_value ? 1 : 0) : ((BRANCH && POLICY) ? nsteps + (bp.bootstrap ? 1 : 0) : nsteps);
-    // BRANCH with POLICY: the row's last step truncated it without terminating it: its V(o') is due
-    bool bp_pend = false;
-    for (int sstep = 0; sstep < niter; ++sstep) {
-    // MULTI: the constants are re-read (scalar cache) each step rather than kept live across the
-    // loop, where ~130 of them would spill out of the SGPR file
-    const Params<float>& P = BAKED ? PB : (MULTI ? *reload_params(Pa) : P0);
-    const int64_t so = MULTI ? (int64_t)sstep * n : 0;   // first row of this step's inputs / outputs
-    float4 act;
-    if constexpr (AC) {
-        const hgp::Eval ev = hgp::policy_eval(pw, pol.pk, pobs, lane, seed_p, (uint64_t)(envoff_p + blk0 + lo), step, epi,
-                                              sstep < nsteps);
-        // the previous step's next_value where that step did not reset: this observation's value
-        if (ac.next_value && sstep > 0 && active && !ac_prev_reset)
-            st_lane<kNTS>(ac.next_value + (so - n) + blk0, (uint32_t)tid, ac_prev_term ? 0.f : ev.v);
-        if (sstep == nsteps) break;
-        act = ev.a;
-        if (active) {
-            st_lane<kNTS>(reinterpret_cast<f32x4*>(pol.actions_out) + so + blk0, (uint32_t)tid,
-                          f32x4{act.x, act.y, act.z, act.w});
-            if (ac.logp) st_lane<kNTS>(ac.logp + so + blk0, (uint32_t)tid, ev.logp);
-            if (ac.value) st_lane<kNTS>(ac.value + so + blk0, (uint32_t)tid, ev.v);
-        }
-    } else if constexpr (BRANCH && POLICY) {
-        const hgp::Eval ev = hgp::policy_eval(pw, pol.pk, pobs, lane, seed_p, 0, 0, 0, false);
-        if (bp.bootstrap) {   // (uniform) br_disc here is the discount after the previous step's multiply
-            const bool boot = bp_pend || (sstep == nsteps && br_alive);
-            br_G = boot ? fmaf(br_disc, bp.value_scale * ev.v, br_G) : br_G;
-            bp_pend = false;
-        }
-        if (sstep == nsteps || !__any(br_alive)) break;   // (wave-uniform)
-        float4 res = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (bp.residual) res = ld_lane(reinterpret_cast<const float4*>(bp.residual) + so + blk0, lo);
-        act = hgp::residual_action(ev.a, res, bp.residual != nullptr, bp.box);
-    } else if constexpr (POLICY) {
-        act = hgp::policy_action(pw, pol.pk, pobs, lane, seed_p, (uint64_t)(envoff_p + blk0 + lo), step, epi);
-        if (active)
-            st_lane<kNTS>(reinterpret_cast<f32x4*>(pol.actions_out) + so + blk0, (uint32_t)tid,
-                          f32x4{act.x, act.y, act.z, act.w});
-    } else {
-        act = ld_lane(reinterpret_cast<const float4*>(a.actions) + so + blk0, lo);
-    }
-    // terrain texels under the committed position (F6): issued now, combined after the wind step
-    const hg::GroundCell<float> cell_c = hg::ground_cell(P, hs[15], hs[16]);
-    const hg::GroundTexels tex_c = hg::ground_fetch(a.hmap, cell_c);
-
-    TSTAMP(1, "v"(hs[17]), "v"(act.w), "v"(epi), "v"(carry[3]), "v"(ws[4]));
-    float W[3];
-    hg::StepCtx ctx;
-    hg::RK4Step<NT, (HELP > 0)> rk;   // NT: the launch is one wave per SIMD; HELP: stage 1 split
-    if constexpr (HELP > 0) {
-        // the wind-independent part of the step's shared context and of stage 1 (kinematics, gear)
-        // while the helper wave runs the wind
-        const hg::Ground<float> h_c = hg::ground_combine<float>(tex_c, cell_c);
-        ctx = hg::step_ctx(P, act.x, act.y, act.z, act.w, 0.f, 0.f, 0.f, h_c, hs[17]);
-#if HG_EARLY_PAIRS
-        rk.begin(P, ctx, hs, hg::att0(hs), Kpairs);
-#else
-        rk.begin(P, ctx, hs, hg::att0(hs));
-#endif
-        TSTAMP(2, "v"(ctx.z0), "v"(hs[0]));   // (HELP: the wind-independent context and stage-1 share done)
-        asm volatile("s_barrier" ::: "memory");
-        TSTAMP(3, "v"(tid));                  // (HELP: past the hand-off barrier)
-        const float* sw = s_wind + wv * 8 * 64 + lane;
-        W[0] = sw[0]; W[1] = sw[64]; W[2] = sw[128];
-#pragma unroll
-        for (int c = 0; c < 5; ++c) ws[c] = sw[(3 + c) * 64];
-        ctx.W0 = W[0]; ctx.W1 = W[1]; ctx.W2 = W[2];
-        TSTAMP(4, "v"(W[0]), "v"(ws[4]));     // (HELP: the wind read from LDS)
-    } else {
-    // turbulence noise (wind_dynamics.py:49-52): injected, or Philox normals
-    float eta[3];
-    if constexpr (BRANCH) {
-        // the env's own noise, whichever row this is (keyed by its global id and the row's counters, which
-        // advance as the env's will), or none
-        if constexpr (ETA) eta[0] = eta[1] = eta[2] = 0.f;
-        else draw_eta<false>(a, seed_p, envoff_p, P, 0, (int64_t)b_env, 0u, step, epi, eta);
-    } else {
-        draw_eta<ETA>(a, seed_p, envoff_p, P, so, blk0, lo, step, epi, eta);
-    }
-
-    // ground height under the committed position (F6), wind step (Heli.step :195-199)
-    TSTAMP(2, "v"(eta[2]), "v"(eta[0]));
-    if constexpr (WEATHER) hg::wind_step_f32<NT>(P, lw, ws, carry, eta, W);
-    else hg::wind_step_f32<NT>(P, ws, carry, eta, W);   // (the lone-wave kernels: the uniform-branch form)
-    TSTAMP(3, "v"(W[2]), "v"(W[0]));
-    const hg::Ground<float> h_c = hg::ground_combine<float>(tex_c, cell_c);
-
-    TSTAMP(4, "v"(h_c.delta), "v"(h_c.hi));
-    ctx = hg::step_ctx(P, act.x, act.y, act.z, act.w, W[0], W[1], W[2], h_c, hs[17]);
-#if HG_EARLY_PAIRS
-    rk.begin(P, ctx, hs, hg::att0(hs), Kpairs);
-#else
-    rk.begin(P, ctx, hs, hg::att0(hs));
-#endif
-    }
-    // RK4 (dynamics.py:158-171); observation from the stage-4 input (F5)
-    float k[18], obs[17];
-    rk.finish(P, ctx, hs, k, obs);
-#if HG_EARLY_POST
-    // the terrain texels under the post-step position (the flags' ground height), requested now so
-    // that their latency hides behind the wraps and the reward
-    const hg::GroundCell<float> cell_p = hg::ground_cell(P, hs[15], hs[16]);
-    const hg::GroundTexels tex_p = hg::ground_fetch(a.hmap, cell_p);
-#endif
-    TSTAMP(8, "v"(hs[8]), "v"(hs[11]), "v"(obs[16]));
-    if (FEAT && !BRANCH && P.reset_retrim && active && !(P.autoreset_next && step < 0)) {   // F8: a reset trims against this wind
-        float* wb = a.retrim_wind + blk0;   // [3][N]: three coalesced rows
-        st_lane<false>(wb, (uint32_t)tid, W[0]);
-        st_lane<false>(wb + n, (uint32_t)tid, W[1]);
-        st_lane<false>(wb + 2 * n, (uint32_t)tid, W[2]);
-    }
-    // step_after (helicopter_dynamics.py:73-77)
-    // utils.py pi_bound, (x + pi) % 2pi - pi.  An angle already in [-pi, pi) is kept as is -- what
-    // the reference's fp64 arithmetic returns to 1e-16, where the fp32 round trip through x + pi
-    // costs up to half an ulp of pi.  The rotor azimuths wrap in nearly every wave every step; the
-    // flapping and euler angles only in a wave-uniform branch taken when one of them left the range.
-    // (The rotor azimuths' wrap is az_advance's.)
-    {
-        const int ang[5] = {4, 5, 12, 13, 14};
-        // every angle in (-pi, pi) <=> the largest |angle| below fp32 pi (two v_max3 with |.| operand
-        // modifiers and one compare instead of five range tests; a NaN angle drops out of the max
-        // and stays NaN either way)
-        const float amax = fmaxf(fmaxf(fmaxf(fabsf(hs[4]), fabsf(hs[5])), fabsf(hs[12])),
-                                 fmaxf(fabsf(hs[13]), fabsf(hs[14])));
-        const bool all_in = amax < 3.14159274101257324f;
-        if (__any(!all_in)) {
-#pragma unroll
-            for (int j = 0; j < 5; ++j) {
-                const float x = hs[ang[j]];
-                hs[ang[j]] = in_pi_range(x) ? x : hg::pi_bound(x);
-            }
-        }
-    }
-
-    TSTAMP(9, "v"(hs[0]));
-    // reward (helicopter_with_tasks.py) and flags (helicopter.py:201-205, 219-240)
-    bool success_step = false;
-    float rew = 0.f;
-    if (TASK == HG_TASK_HOVER) rew = hg::reward_hover(P, hs, k, &success_step);
-    if (TASK == HG_TASK_FORWARD_FLIGHT) rew = hg::reward_forward(P, hs, k, &success_step);
-#if HG_EARLY_POST
-    const hg::Ground<float> h_post = hg::ground_combine<float>(tex_p, cell_p);
-#else
-    const hg::Ground<float> h_post = hg::ground_height(P, a.hmap, hs[15], hs[16]);
-#endif
-    const bool waiting = step < 0;   // ended last step, reset due now (next-step auto-reset)
-    step += 1;
-    const bool failed = hg::is_failed(P, hs, k, h_post);
-    TSTAMP(10, "v"(rew), "v"((int)failed));
-    const bool successed = succ >= P.success_steps;   // successed_time before this step's add
-    const bool time_up = step >= P.time_up_steps;
-    // next-step auto-reset: an env that ended last step (counter -(n + 1)) only resets this step
-    const bool pending = FEAT && !BRANCH && P.autoreset_next && waiting;   // (BRANCH: such a row is not alive)
-    const bool term = (failed || successed) && !pending;
-    const bool trunc = (time_up || (FEAT && step >= P.max_episode_steps)) && !pending;   // + TimeLimit
-    const bool done = term || trunc;
-    succ += success_step ? 1 : 0;
-
-    if constexpr (BRANCH) {
-        // the row's accumulation, masked by select: a row past its end keeps stepping beside its live
-        // neighbours (physics.h clamps the terrain indices of a non-finite position) and adds nothing
-        br_G = br_alive ? fmaf(br_disc, rew, br_G) : br_G;
-        br_disc = br_disc * br.gamma;
-        br_T += br_alive ? 1 : 0;
-        br_end = (br_alive && done) ? (uint32_t)((failed ? HG_INFO_FAILED : 0) | (successed ? HG_INFO_SUCCESSED : 0) |
-                                                 (time_up ? HG_INFO_TIME_UP : 0) | (success_step ? HG_INFO_SUCCESS_STEP : 0))
-                                    : br_end;
-        if constexpr (POLICY) bp_pend = bp.bootstrap && br_alive && trunc && !term;
-        br_alive = br_alive && !done;
-        // (wave-uniform; POLICY: a lane's pending bootstrap takes the next iteration's forward pass)
-        if (!__any(POLICY ? (br_alive || bp_pend) : br_alive)) break;
-        if constexpr (POLICY) {
-#pragma unroll
-            for (int c = 0; c < 17; ++c) pobs[c] = obs[c];
-        }
-        carry[0] = obs[4];
-        carry[1] = obs[5];
-        carry[2] = obs[6];
-        carry[3] = obs[16];
-        continue;   // no outputs per step, no reset
-    }
-
-    // auto-reset (same step, or the step after the end)
-    const bool do_reset = P.autoreset && active && ((FEAT && P.autoreset_next) ? pending : done);
-    // a reset whose trim runs concurrently with this step -- a next-step reset in ov mode, any reset in
-    // a fused launch: only the step counter is stored here, the trim writes the rest
-#ifndef HG_FUSED_NOTRIM   // diagnostic: 1, a fused launch's trim blocks leave at once and its resets
-#define HG_FUSED_NOTRIM 0   // take the template (the step's own cost in that launch)
-#endif
-    const bool defer = FEAT && (a.ov_active || (a.fused_ctr && !HG_FUSED_NOTRIM)) && do_reset;
-    defer_st = defer;
-    if (active) {
-        st_lane<kNTS>(a.reward + so + blk0, (uint32_t)tid, pending ? 0.f : rew);
-        st_lane<kNTS>(a.terminated + so + blk0, (uint32_t)tid, (uint8_t)term);
-        st_lane<kNTS>(a.truncated + so + blk0, (uint32_t)tid, (uint8_t)trunc);
-        if (a.info)
-            st_lane<kNTS>(a.info + so + blk0, (uint32_t)tid, pending ? (uint8_t)0 : (uint8_t)((failed ? HG_INFO_FAILED : 0) | (successed ? HG_INFO_SUCCESSED : 0) |
-                                  (time_up ? HG_INFO_TIME_UP : 0) | (success_step ? HG_INFO_SUCCESS_STEP : 0) |
-                                  (do_reset ? HG_INFO_RESET : 0)));
-    }
-    // uncompacted reset info (hg_step_rows): the terminal observation at the env's own row, in a
-    // wave-uniform branch taken only by waves with a reset
-    if (!MULTI && a.final_obs_rows && __ballot(do_reset)) {
-        if (do_reset) {   // the 68-byte row as four 16-byte stores and one dword (dword-aligned rows)
-            typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-            f4u* row = reinterpret_cast<f4u*>(a.final_obs_rows + i * 17);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) row[q] = f4u{obs[4 * q], obs[4 * q + 1], obs[4 * q + 2], obs[4 * q + 3]};
-            a.final_obs_rows[i * 17 + 16] = obs[16];
-        }
-    }
-
-    if constexpr (AC) {
-        // next_value of a lane this step resets: V of its terminal observation (`obs`, before the reset
-        // below overwrites it), 0 where it terminated.  The forward pass runs only in waves with a lane
-        // that was truncated and reset, and then in all 64 lanes: the matrix instructions take every
-        // column, and a column's result depends on that column alone.
-        if (ac.next_value) {
-            if (__any(do_reset)) {
-                float vt = 0.f;
-                if (__any(do_reset && !term))
-                    vt = hgp::policy_eval(pw, pol.pk, obs, lane, seed_p, 0, 0, 0, false).v;
-                if (do_reset) st_lane<kNTS>(ac.next_value + so + blk0, (uint32_t)tid, term ? 0.f : vt);
-            }
-            ac_prev_reset = do_reset;
-            ac_prev_term = term;
-        }
-    }
-
-    // compacted reset info with a wave-ballot compaction (HG_RT_QUEUE_LATE: as the re-trim queue
-    // below, the slots used after the state stores, the terminal observations kept until then)
-    if (FEAT && P.autoreset && a.reset_count) {
-        if constexpr (kRtLate) asm volatile("" ::"v"(tpl));
-        const unsigned long long mask = __ballot(do_reset);
-        if constexpr (kRtLate) {
-            rc_mask = mask;
-            if (mask) {
-                const int leader = __ffsll((long long)mask) - 1;
-                if (lane == leader) rc_base = atomicAdd(a.reset_count, __popcll(mask));
-            }
-#pragma unroll
-            for (int c = 0; c < 17; ++c) fo[c] = obs[c];
-            rc_job = do_reset;
-        } else if (mask) {
-            const int leader = __ffsll((long long)mask) - 1;
-            int base = 0;
-            if (lane == leader) base = atomicAdd(a.reset_count, __popcll(mask));
-            base = __shfl(base, leader);
-            if (do_reset) {
-                const int slot = base + __popcll(mask & ((1ull << lane) - 1ull));
-                if (a.reset_index && slot < n) a.reset_index[slot] = (int32_t)i;
-                if (a.final_obs && slot < n) {
-#pragma unroll
-                    for (int c = 0; c < 17; ++c) a.final_obs[(int64_t)slot * 17 + c] = obs[c];
-                }
-            }
-        }
-    }
-    if (FEAT && a.ov_recs) {   // ov mode: the episodes ending now, trimmed while the next step runs
-        const bool ends = active && done && P.autoreset;
-        const unsigned long long mask = __ballot(ends);
-        if (mask) {
-            const int leader = __ffsll((long long)mask) - 1;
-            int base = 0;
-            if (lane == leader) base = atomicAdd(a.ov_count, __popcll(mask));
-            base = __shfl(base, leader);
-            const int slot = base + __popcll(mask & ((1ull << lane) - 1ull));
-            if (ends && slot < n)
-                a.ov_recs[slot] = make_int4((int32_t)i, __float_as_int(W[0]), __float_as_int(W[1]), __float_as_int(W[2]));
-        }
-    }
-    // queue the resets for retrim_kernel (which overwrites the template).  HG_RT_QUEUE_LATE: the slot
-    // counter's atomic is issued here and its value used after the state stores (lone-wave
-    // kernels, one step per launch: 65 536 envs same-step re-trim 30.43 -> 30.11 us), so that the round trip of the device-scope atomic overlaps them instead of lengthening
-    // the wave (the library is built without the atomic optimizer, which would read the value here)
-    if (FEAT && P.reset_retrim) {
-        // the reset template's load (issued at the start) waited for here, not after the atomic
-        if constexpr (kRtLate) asm volatile("" ::"v"(tpl));
-        rt_job = do_reset && !a.ov_active;
-        rt_mask = __ballot(rt_job);
-        if (a.fused_ctr) {
-            // fused: every wave counts itself, so that the trim waves know the queue is complete once
-            // the count reaches the wave count.  A wave with jobs reserves them and counts itself in
-            // one atomic (its jobs in the low word, itself in the high word); a wave without, in one of
-            // kFusedWaveCtrs counters on lines of their own, without waiting for the old value: every
-            // wave on one address serialised the atomics (65 536 envs: the step waves ended 10 to 45 us
-            // into the launch, scripts/fused_probe.py)
-            if (rt_mask) {
-                const int leader = __ffsll((long long)rt_mask) - 1;
-                if (lane == leader)
-                    rt_base = (int)(uint32_t)atomicAdd(a.fused_ctr, (1ull << 32) | (unsigned long long)__popcll(rt_mask));
-            } else if (lane == 0) {
-                int32_t* wc = reinterpret_cast<int32_t*>(a.fused_ctr) + kFusedLine * (1 + (int)(bid % kFusedWaveCtrs));
-                __hip_atomic_fetch_add(wc, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        } else if (rt_mask) {
-            const int leader = __ffsll((long long)rt_mask) - 1;
-            if (lane == leader) rt_base = atomicAdd(a.retrim_count + (a.retrim_slot > 0 ? a.retrim_slot : 0), __popcll(rt_mask));
-        }
-        rt_next = P.autoreset_next;
-        rw0 = W[0];   // the job's trim wind (same-step reset; a next-step reset reads its own, below)
-        rw1 = W[1];
-        rw2 = W[2];
-    }
-    if (!kRtLate) rt_queue();
-    if (FEAT && P.env_templates) {   // this env's own reset target (its own trim condition)
-        if (do_reset) {
-            const float* tr = a.tmpl_env + (int64_t)i * kTplFloats;
-#pragma unroll
-            for (int c = 0; c < 18; ++c) hs[c] = tr[c];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) carry[c] = tr[18 + c];
-#pragma unroll
-            for (int c = 0; c < 17; ++c) obs[c] = tr[22 + c];
-            // the loads complete inside this branch (vmcnt(0)): the memory-counter waits after the join
-            // then need not count the re-trim queue's atomic on the other path
-            if constexpr (kRtLate) __builtin_amdgcn_s_waitcnt(0xF70);
-        }
-    } else if (__ballot(do_reset)) {
-#if HG_TIMING
-        HG_STAGE_FLAG(1);
-#endif
-        // Template<float> = heli[18] | carry[4] | obs[17], float c held by lane c.  The readlanes run
-        // in this wave-uniform branch (every lane has loaded its template float), the selects per lane.
-#pragma unroll
-        for (int c = 0; c < 18; ++c) {
-            const float v = lane_value(tpl, c);
-            hs[c] = do_reset ? v : hs[c];
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float v = lane_value(tpl, 18 + c);
-            carry[c] = do_reset ? v : carry[c];
-        }
-#pragma unroll
-        for (int c = 0; c < 17; ++c) {
-            const float v = lane_value(tpl, 22 + c);
-            obs[c] = do_reset ? v : obs[c];
-        }
-    }
-    if constexpr (NT) {
-        // the lone-wave kernels: the same assignments as selects, no divergent branch (65 536 envs
-        // -0.08 us; the bulk variant keeps the branch)
-#pragma unroll
-        for (int c = 0; c < 5; ++c) ws[c] = do_reset ? 0.f : ws[c];
-        carry[0] = do_reset ? carry[0] : obs[4];
-        carry[1] = do_reset ? carry[1] : obs[5];
-        carry[2] = do_reset ? carry[2] : obs[6];
-        carry[3] = do_reset ? carry[3] : obs[16];
-        step = do_reset ? 0 : ((FEAT && P.autoreset_next && done) ? -step - 1 : step);
-        succ = do_reset ? 0 : succ;
-        epi = do_reset ? epi + 1 : epi;
-    } else if (do_reset) {
-#pragma unroll
-        for (int c = 0; c < 5; ++c) ws[c] = 0.f;
-        step = 0;
-        succ = 0;
-        epi += 1;
-    } else {
-        carry[0] = obs[4];
-        carry[1] = obs[5];
-        carry[2] = obs[6];
-        carry[3] = obs[16];
-        if (FEAT && P.autoreset_next && done) step = -step - 1;   // reset on the next step (n = step kept)
-    }
-    uint64_t skip_rows = 0;
-    if (FEAT && !MULTI) skip_rows = __ballot(defer);
-    store_obs_wave<kNTS, MULTI>(s_obs + wv * 64 * HG_N_OBS, obs, a.obs, so, blk0, n, lane, skip_rows);
-    if constexpr (POLICY) {
-#pragma unroll
-        for (int c = 0; c < 17; ++c) pobs[c] = obs[c];
-    }
-    }   // steps
-    if constexpr (BRANCH) {   // the row's three results; the env's state stays as it was read
-        if (active) {
-            st_lane<kNTS>(br.ret + blk0, (uint32_t)tid, br_G);
-            if (br.alive_steps) st_lane<kNTS>(br.alive_steps + blk0, (uint32_t)tid, br_T);
-            if (br.end_info) st_lane<kNTS>(br.end_info + blk0, (uint32_t)tid, (uint8_t)br_end);
-        }
-        return;
-    }
-    TSTAMP(13, "v"(hs[0]), "v"(carry[3]));
-    st_b = reinterpret_cast<f32x4*>(state_p + tile * kTileWords) + 4 * kTileEnvs;
-    asm volatile("" : "+s"(st_b));
-    if (FEAT && !MULTI && __ballot(defer_st)) {   // a deferred reset: its step counter only (the trim writes the rest)
-        if (defer_st) reinterpret_cast<int32_t*>(GRP(st_b, 0) + tid)[3] = 0;
-    }
-    if (active && !(FEAT && !MULTI && defer_st)) {
-        // the lane index re-materialised in this block, so that each store selects the SGPR-base
-        // form (a 32-bit lane offset) instead of a 64-bit VALU address add per store
-        uint32_t t = (uint32_t)tid;
-        asm volatile("" : "+v"(t));
-        st_lane<kNTS>(GRP(st_b, 0), t, f32x4{hs[15], hs[16], hs[17], __int_as_float(step)});
-        st_lane<kNTS>(GRP(st_b, 1), t, f32x4{__int_as_float(epi), __int_as_float(succ), carry[3], carry[0]});
-        st_lane<kNTS>(GRP(st_b, 2), t, f32x4{carry[1], carry[2], ws[0], ws[1]});
-        st_lane<kNTS>(GRP(st_b, 3), t, f32x4{ws[2], ws[3], ws[4], hs[14]});
-        st_lane<kNTS>(GRP(st_b, 4), t, f32x4{hs[0], hs[1], hs[4], hs[5]});
-        st_lane<kNTS>(GRP(st_b, 5), t, f32x4{hs[6], hs[7], hs[8], hs[9]});
-        st_lane<kNTS>(GRP(st_b, 6), t, f32x4{hs[10], hs[11], hs[12], hs[13]});
-    }
-#undef GRP
-    if (kRtLate) rt_queue();
-    if constexpr (kRtLate) {
-        if (FEAT && rc_mask) {
-            const int leader = __ffsll((long long)rc_mask) - 1;
-            const int slot = __builtin_amdgcn_readlane(rc_base, leader) + __popcll(rc_mask & ((1ull << lane) - 1ull));
-            if (rc_job && slot < n) {
-                if (a.reset_index) a.reset_index[slot] = (int32_t)i;
-                if (a.final_obs) {
-#pragma unroll
-                    for (int c = 0; c < 17; ++c) a.final_obs[(int64_t)slot * 17 + c] = fo[c];
-                }
-            }
-        }
-    }
-
-    TSTAMP(11, "v"(tid));
-#if HG_TIMING
-    __builtin_amdgcn_s_waitcnt(0);
-    TSTAMP(12, "v"(tid));
-    if ((tid & 63) == 0 && (i >> 6) < HG_TIMING_WAVES) g_timing[i >> 6][14] = __builtin_amdgcn_s_memrealtime();
-#endif
-}
-
-template <int TASK, bool ETA, bool NT, bool FEAT, bool MULTI, bool BAKED, bool NTS>
-__global__ __launch_bounds__(kStepBlock, NT ? HG_MIN_WAVES : HG_MIN_WAVES_BULK) void step_kernel(float* __restrict__ state_p, int64_t n_p, uint64_t seed_p,
-                                                      int64_t envoff_p, ParamArg Pa,
-                                                      const Template<float>* __restrict__ Tp, const StepArgs a) {
-    step_body<TASK, ETA, NT, FEAT, MULTI, BAKED, NTS>(state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x);
-}
-
-// Small batches (up to half a wave per SIMD): each block is a tile's wave and a helper wave that runs
-// the tile's noise and wind step (no input from the helicopter state) while the tile's wave loads
-// its state and forms the rest of the step's context (density, controls, terrain, attitude
-// sin/cos), the wind handed over in LDS at one barrier.  Bitwise the one-wave kernel (tested).
-// Per step, against the one-wave kernel: 4 096 envs 5.80 -> 5.63 us, 16 384 6.29 -> 6.08,
-// 32 768 6.73 -> 6.63 (profiles/r04_helper_ab.txt).  Not used at a wave per SIMD, where the helpers
-// share SIMDs with the stepping waves: 65 536 envs 7.39 -> 7.44 us (blocks of 2 or 4 tiles with their
-// helpers: 8.81, 7.59).
-#ifndef HG_HELPER   // tiles per block in the small-batch helper kernel; 0: none
-#define HG_HELPER 1
-#endif
-#ifndef HG_HELPER_DIV   // the helper kernel up to resident_envs / HG_HELPER_DIV envs (2: two tiles per CU)
-#define HG_HELPER_DIV 2
-#endif
-#if HG_HELPER > 0
-template <int TASK, bool FEAT, bool BAKED>
-__global__ __launch_bounds__(128 * HG_HELPER, 1) void step_help_kernel(float* __restrict__ state_p, int64_t n_p, uint64_t seed_p,
-                                                                    int64_t envoff_p, ParamArg Pa,
-                                                                    const Template<float>* __restrict__ Tp, const StepArgs a) {
-    step_body<TASK, false, true, FEAT, false, BAKED, false, HG_HELPER>(state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x);
-}
-#endif
-
-#ifndef HG_RTC
 // hg_rollout_policy: the rollout with the handle's MLP policy evaluated in the kernel.  One wave per
 // block and at most one wave per SIMD, deliberately: the policy's matrix operands (117 registers per
 // lane, policy_mlp.h) stay in registers across the steps beside the two layers' accumulators (128)
@@ -1139,8 +77,10 @@ __global__ __launch_bounds__(64, 1) void rollout_policy_kernel(float* __restrict
                                                                int64_t envoff_p, ParamArg Pa,
                                                                const Template<float>* __restrict__ Tp, const StepArgs a,
                                                                const PolicyArgs pol) {
-    step_body<TASK, ETA, true, FEAT, true, BAKED, false, 0, true>(state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x,
-                                                                  pol);
+    StepExtras x;
+    x.pol = &pol;
+    step_body<TASK, kNT | kMulti | kPolicy | (ETA ? kEta : 0) | (FEAT ? kFeat : 0) | (BAKED ? kBaked : 0)>(
+        state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, x);
 }
 
 // hg_rollout_pop: rollout_policy_kernel (in-kernel noise) in which the wave of state tile t reads the packed
@@ -1154,8 +94,10 @@ __global__ __launch_bounds__(64, 1) void rollout_pop_kernel(float* __restrict__ 
                                                             const PolicyArgs pol, const uint32_t tiles_per_member) {
     PolicyArgs mine = pol;
     mine.pk = pol.pk + (size_t)(blockIdx.x / tiles_per_member) * hgp::kPolicyFloats;
-    step_body<TASK, false, true, FEAT, true, BAKED, false, 0, true>(state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x,
-                                                                    mine);
+    StepExtras x;
+    x.pol = &mine;
+    step_body<TASK, kNT | kMulti | kPolicy | (FEAT ? kFeat : 0) | (BAKED ? kBaked : 0)>(state_p, n_p, seed_p, envoff_p, Pa, Tp,
+                                                                                         a, blockIdx.x, x);
 }
 
 // hg_rollout_ac: rollout_policy_kernel with the log-probabilities and the value head's values (step_body's
@@ -1166,8 +108,11 @@ __global__ __launch_bounds__(64, 1) void rollout_ac_kernel(float* __restrict__ s
                                                            int64_t envoff_p, ParamArg Pa,
                                                            const Template<float>* __restrict__ Tp, const StepArgs a,
                                                            const PolicyArgs pol, const AcArgs ac) {
-    step_body<TASK, ETA, true, FEAT, true, BAKED, false, 0, true, true>(state_p, n_p, seed_p, envoff_p, Pa, Tp, a,
-                                                                        blockIdx.x, pol, ac);
+    StepExtras x;
+    x.pol = &pol;
+    x.ac = &ac;
+    step_body<TASK, kNT | kMulti | kPolicy | kAc | (ETA ? kEta : 0) | (FEAT ? kFeat : 0) | (BAKED ? kBaked : 0)>(
+        state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, x);
 }
 
 // Per-env weather (hg_set_weather): the step, the rollout and the two policy rollouts with step_body's
@@ -1179,16 +124,21 @@ template <int TASK, bool ETA, bool NT, bool MULTI, bool BAKED>
 __global__ __launch_bounds__(kStepBlock, NT ? HG_MIN_WAVES : HG_MIN_WAVES_BULK) void step_weather_kernel(
     float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
     const Template<float>* __restrict__ Tp, const StepArgs a, const WeatherArgs wx) {
-    step_body<TASK, ETA, NT, true, MULTI, BAKED, false, 0, false, false, false, true>(
-        state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, PolicyArgs{}, AcArgs{}, BranchArgs{}, BranchPolicyArgs{}, wx);
+    StepExtras x;
+    x.wx = &wx;
+    step_body<TASK, kFeat | kWeather | (ETA ? kEta : 0) | (NT ? kNT : 0) | (MULTI ? kMulti : 0) | (BAKED ? kBaked : 0)>(
+        state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, x);
 }
 
 template <int TASK, bool ETA, bool BAKED>
 __global__ __launch_bounds__(64, 1) void rollout_policy_weather_kernel(
     float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
     const Template<float>* __restrict__ Tp, const StepArgs a, const PolicyArgs pol, const WeatherArgs wx) {
-    step_body<TASK, ETA, true, true, true, BAKED, false, 0, true, false, false, true>(
-        state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, pol, AcArgs{}, BranchArgs{}, BranchPolicyArgs{}, wx);
+    StepExtras x;
+    x.pol = &pol;
+    x.wx = &wx;
+    step_body<TASK, kNT | kFeat | kMulti | kPolicy | kWeather | (ETA ? kEta : 0) | (BAKED ? kBaked : 0)>(
+        state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, x);
 }
 
 template <int TASK, bool ETA, bool BAKED>
@@ -1196,8 +146,12 @@ __global__ __launch_bounds__(64, 1) void rollout_ac_weather_kernel(
     float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
     const Template<float>* __restrict__ Tp, const StepArgs a, const PolicyArgs pol, const AcArgs ac,
     const WeatherArgs wx) {
-    step_body<TASK, ETA, true, true, true, BAKED, false, 0, true, true, false, true>(
-        state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, pol, ac, BranchArgs{}, BranchPolicyArgs{}, wx);
+    StepExtras x;
+    x.pol = &pol;
+    x.ac = &ac;
+    x.wx = &wx;
+    step_body<TASK, kNT | kFeat | kMulti | kPolicy | kAc | kWeather | (ETA ? kEta : 0) | (BAKED ? kBaked : 0)>(
+        state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, x);
 }
 
 // hg_rollout_pop on a weather handle: rollout_pop_kernel's member offset in front of the weather rollout
@@ -1208,8 +162,11 @@ __global__ __launch_bounds__(64, 1) void rollout_pop_weather_kernel(
     const WeatherArgs wx) {
     PolicyArgs mine = pol;
     mine.pk = pol.pk + (size_t)(blockIdx.x / tiles_per_member) * hgp::kPolicyFloats;
-    step_body<TASK, false, true, true, true, BAKED, false, 0, true, false, false, true>(
-        state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, mine, AcArgs{}, BranchArgs{}, BranchPolicyArgs{}, wx);
+    StepExtras x;
+    x.pol = &mine;
+    x.wx = &wx;
+    step_body<TASK, kNT | kFeat | kMulti | kPolicy | kWeather | (BAKED ? kBaked : 0)>(state_p, n_p, seed_p, envoff_p, Pa, Tp, a,
+                                                                                       blockIdx.x, x);
 }
 
 // hg_rollout_branch: the rollout's steps on N * branches rows that start from the N envs' states
@@ -1228,8 +185,10 @@ __global__ __launch_bounds__(kStepBlock, WAVES) void rollout_branch_kernel(
     float* __restrict__ state_p, int64_t rows_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
     const Template<float>* __restrict__ Tp, const StepArgs a, const BranchArgs br) {
     static_assert(WAVES >= 1 && WAVES <= 3, "WAVES 1, 2: the lone-wave step; 3: the bulk step");
-    step_body<TASK, NOISE_OFF, (WAVES < 3), true, true, BAKED, false, 0, false, false, true>(
-        state_p, rows_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, PolicyArgs{}, AcArgs{}, br);
+    StepExtras x;
+    x.br = &br;
+    step_body<TASK, kFeat | kMulti | kBranch | (NOISE_OFF ? kEta : 0) | (WAVES < 3 ? kNT : 0) | (BAKED ? kBaked : 0)>(
+        state_p, rows_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, x);
 }
 
 // hg_rollout_branch_policy: rollout_branch_kernel's rows with the handle's policy inside them (step_body's
@@ -1243,8 +202,12 @@ __global__ __launch_bounds__(64, 1) void rollout_branch_policy_kernel(
     float* __restrict__ state_p, int64_t rows_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
     const Template<float>* __restrict__ Tp, const StepArgs a, const PolicyArgs pol, const BranchArgs br,
     const BranchPolicyArgs bp) {
-    step_body<TASK, NOISE_OFF, true, true, true, BAKED, false, 0, true, false, true>(
-        state_p, rows_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, pol, AcArgs{}, br, bp);
+    StepExtras x;
+    x.pol = &pol;
+    x.br = &br;
+    x.bp = &bp;
+    step_body<TASK, kNT | kFeat | kMulti | kPolicy | kBranch | (NOISE_OFF ? kEta : 0) | (BAKED ? kBaked : 0)>(
+        state_p, rows_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, x);
 }
 
 // hg_mppi_sample: candidate action sequences around a nominal one, element-wise over [horizon, N*branches]:
@@ -1415,8 +378,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
         if (kStepBlock == 64 || threadIdx.x < 64) hgk::retrim_jobs(r, blockIdx.x, tb, rcount, rrecs, rT, rP, 0);
         return;
     }
-    step_body<TASK, false, true, true, false, BAKED, false>(state_p, n_p, seed_p, envoff_p, Pa, Tp, a,
-                                                             (int64_t)blockIdx.x - tb);
+    step_body<TASK, kNT | kFeat | (BAKED ? kBaked : 0)>(state_p, n_p, seed_p, envoff_p, Pa, Tp, a, (int64_t)blockIdx.x - tb);
 }
 
 // reset_mode RETRIM with same-step auto-reset, lone-wave sizes: one launch holds the step and the trims
@@ -1441,14 +403,8 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
             hgk::retrim_jobs<true>(r, blockIdx.x, tb, rcount, rrecs, rT, rP, 0);
         return;
     }
-    step_body<TASK, false, true, true, false, BAKED, false>(state_p, n_p, seed_p, envoff_p, Pa, Tp, a,
-                                                             (int64_t)blockIdx.x - tb);
+    step_body<TASK, kNT | kFeat | (BAKED ? kBaked : 0)>(state_p, n_p, seed_p, envoff_p, Pa, Tp, a, (int64_t)blockIdx.x - tb);
 }
-#endif
-
-#ifdef HG_RTC   // step_rtc.hip: the step kernel's code and nothing else
-}  // namespace
-#else
 
 // reset_mode RETRIM bookkeeping: the wind each env's next reset is trimmed against (the mean wind
 // until the env has stepped, helicopter.py:55), and the compacted list of masked envs of hg_reset.
@@ -2328,65 +1284,74 @@ static inline unsigned retrim_grid(int64_t jobs) {
 }
 
 #define PARAM_ARG(e) ((const Params<float>*)(e)->params_dev)
-// the step kernel's leading (preloaded) parameters
-#define STEP_KARGS(e) (e)->state, (int64_t)(e)->n, (uint64_t)(e)->cfg.seed, (int64_t)(e)->cfg.env_offset, PARAM_ARG(e), \
-                      (e)->tmpl_dev
 
+// Run-time values as compile-time constants: `f`, a generic lambda, is called with one
+// std::integral_constant per lifted value and reads each back with LIFTED.  A launch lifts exactly the
+// template parameters of the kernel it names, so the library holds no kernel that no launch reaches.
+#define LIFTED(c) decltype(c)::value
+template <typename F>
+static auto lift_task(int32_t task, F&& f) {
+    switch (task) {
+        case HG_TASK_HOVER: return f(std::integral_constant<int, HG_TASK_HOVER>{});
+        case HG_TASK_FORWARD_FLIGHT: return f(std::integral_constant<int, HG_TASK_FORWARD_FLIGHT>{});
+        default: return f(std::integral_constant<int, HG_TASK_HELI>{});
+    }
+}
+template <typename F>
+static auto lift_bools(F&& f) {
+    return f();
+}
+template <typename F, typename... B>
+static auto lift_bools(F&& f, bool b, B... rest) {
+    return b ? lift_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
+             : lift_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+
+// A launch of a kernel of the step family: the step's leading (preloaded) parameters -- `n` the handle's
+// envs, or a branched rollout's rows --, StepArgs, then the family's own arguments
+template <typename K, typename... X>
+static void launch_kernel(K kern, const hg_env* e, hipStream_t s, unsigned grid, unsigned block, int64_t n,
+                          const StepArgs& a, const X&... x) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, s, e->state, n, (uint64_t)e->cfg.seed,
+                       (int64_t)e->cfg.env_offset, PARAM_ARG(e), e->tmpl_dev, a, x...);
+}
+static inline unsigned blocks_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
+static inline WeatherArgs weather_args(const hg_env* e) {
+    return WeatherArgs{reinterpret_cast<const f32x4*>(e->wx_rec), e->wx_tep};
+}
+// The lone-wave (NT) step while a launch's envs or rows fit HG_NT_WAVES waves per SIMD, past it the bulk step
+static inline bool lone_wave(const hg_env* e, int64_t n) { return n <= HG_NT_WAVES * e->resident_envs; }
+
+// hg_step*'s launch (MULTI false) and hg_rollout's (MULTI true): task x injected noise x lone-wave or bulk x
+// the optional features x the default airframe's constant-specialised step (baked.h) when the env uses it.
 // Occupancy of launches with more waves than SIMDs: three waves per SIMD (<= 168 VGPRs) at every
 // size.  Until the azimuths left the stepped state, two waves per SIMD (a dynamic-LDS cap) were
 // faster past 2 M envs, where the write-heavy HBM stream binds (4 M: 271 against 284 us); with the
 // 28-word tile three are (4 M: 254.6 against 257.8 us, interleaved A/B), so the cap is gone.
-template <int T, bool ETA, bool NT, bool FEAT, bool MULTI, bool BAKED, bool NTS = false>
-static void launch_step(const hg_env* e, hipStream_t s, const StepArgs& a) {
-#if HG_HELPER > 0
-    if constexpr (NT && !ETA && !MULTI) if (e->n <= e->resident_envs / HG_HELPER_DIV) {
-        const unsigned tiles = (unsigned)((e->n + 63) / 64);
-        hipLaunchKernelGGL((step_help_kernel<T, FEAT, BAKED>), dim3((tiles + HG_HELPER - 1) / HG_HELPER),
-                           dim3(128 * HG_HELPER), 0, s, STEP_KARGS(e), a);
-        ++e->n_launch[3];
-        return;
-    }
-#endif
-    ++e->n_launch[NT ? 4 : 5];
-    const unsigned grid = (unsigned)((e->n + kStepBlock - 1) / kStepBlock);
-    hipLaunchKernelGGL((step_kernel<T, ETA, NT, FEAT, MULTI, BAKED, NTS>), dim3(grid), dim3(kStepBlock), 0, s,
-                       STEP_KARGS(e), a);
-}
-
-// The step variant for a launch: NT (the lone-wave variant) while the batch fits two waves per SIMD;
-// past it the bulk variant, whose per-step launches of the default airframe store their outputs
-// non-temporally too up to four waves per SIMD (NTS: 196 608 envs 15.6 -> 14.7 us, 262 144 forward
-// flight 20.1 -> 20.0 us; from 524 288 envs on, where the outputs of one step are read back by the
-// next one through the Infinity Cache, plain stores are faster: 37.7 against 38.5 us, 1 M 67.1
-// against 69.4 us); the default airframe's constant-specialised kernel (baked.h) when the env uses
-// it; with or without the optional features.
 // (returns the run-time specialised launch's status; the library's own launches report through
 // hipGetLastError)
-#define WEATHER_ARG(e) WeatherArgs{reinterpret_cast<const f32x4*>((e)->wx_rec), (e)->wx_tep}
-// A weather handle's step or rollout: the lone-wave variant while the batch fits two waves per SIMD, the bulk
-// one past it; injected or in-kernel noise; the constant-specialised step when the env uses it.
-template <int T, bool MULTI>
-static void dispatch_step_weather(const hg_env* e, hipStream_t s, const StepArgs& a, bool eta) {
-    const unsigned grid = (unsigned)((e->n + kStepBlock - 1) / kStepBlock);
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kStepBlock), 0, s, STEP_KARGS(e), a, WEATHER_ARG(e)); };
-    auto pick = [&](auto nt) {
-        constexpr bool NT = decltype(nt)::value;
-        ++e->n_launch[NT ? 4 : 5];
-        if (e->baked) eta ? go(step_weather_kernel<T, true, NT, MULTI, true>) : go(step_weather_kernel<T, false, NT, MULTI, true>);
-        else eta ? go(step_weather_kernel<T, true, NT, MULTI, false>) : go(step_weather_kernel<T, false, NT, MULTI, false>);
-    };
-    if (e->n <= HG_NT_WAVES * e->resident_envs) pick(std::true_type{});
-    else pick(std::false_type{});
-}
-
-template <int T, bool MULTI>
-static hipError_t dispatch_step(const hg_env* e, hipStream_t s, const StepArgs& a, bool eta, bool feat) {
-    if (e->weather) {
-        dispatch_step_weather<T, MULTI>(e, s, a, eta);
+template <bool MULTI>
+static hipError_t launch_step(const hg_env* e, hipStream_t s, const StepArgs& a, bool eta, bool feat) {
+    const unsigned grid = blocks_for(e->n, kStepBlock);
+    const bool nt = lone_wave(e, e->n);
+    // NTS: the bulk step's per-step launches of a constant-specialised airframe store their outputs
+    // non-temporally too up to HG_NTS_WAVES waves per SIMD (196 608 envs 15.6 -> 14.7 us, 262 144 forward
+    // flight 20.1 -> 20.0 us; from 524 288 envs on, where the outputs of one step are read back by the
+    // next one through the Infinity Cache, plain stores are faster: 37.7 against 38.5 us, 1 M 67.1
+    // against 69.4 us)
+    const bool nts = !nt && e->n <= HG_NTS_WAVES * e->resident_envs;
+    if (e->weather) {   // per-env weather: kernels of their own, always with the optional features
+        ++e->n_launch[nt ? 4 : 5];
+        lift_task(e->cfg.task, [&](auto t) {
+            lift_bools([&](auto c_eta, auto c_nt, auto c_baked) {
+                launch_kernel(step_weather_kernel<LIFTED(t), LIFTED(c_eta), LIFTED(c_nt), MULTI, LIFTED(c_baked)>, e, s, grid,
+                              kStepBlock, e->n, a, weather_args(e));
+            }, eta, nt, e->baked);
+        });
         return hipSuccess;
     }
     if (!MULTI && !eta && e->rtc) {   // the airframe's run-time specialised kernels, same size rules
-        const int v = e->n <= HG_NT_WAVES * e->resident_envs ? 0 : (e->n <= HG_NTS_WAVES * e->resident_envs ? 2 : 4);
+        const int v = nt ? 0 : (nts ? 2 : 4);
         float* state = e->state;
         int64_t n = e->n, off = (int64_t)e->cfg.env_offset;
         uint64_t seed = (uint64_t)e->cfg.seed;
@@ -2394,188 +1359,110 @@ static hipError_t dispatch_step(const hg_env* e, hipStream_t s, const StepArgs& 
         const Template<float>* tp = e->tmpl_dev;
         StepArgs args = a;
         void* params[] = {&state, &n, &seed, &off, &pa, &tp, &args};
-        const unsigned grid = (unsigned)((e->n + kStepBlock - 1) / kStepBlock);
         ++e->n_launch[2];
         return hipModuleLaunchKernel(e->rtc_fn[v + (feat ? 1 : 0)], grid, 1, 1, kStepBlock, 1, 1, 0, s, params, nullptr);
     }
-    auto pick = [&](auto nt) {
-        constexpr bool NT = decltype(nt)::value;
-        if (e->baked) {
-            if (!NT && !MULTI && e->n <= HG_NTS_WAVES * e->resident_envs) {
-                if (feat) eta ? launch_step<T, true, false, true, false, true, true>(e, s, a) : launch_step<T, false, false, true, false, true, true>(e, s, a);
-                else eta ? launch_step<T, true, false, false, false, true, true>(e, s, a) : launch_step<T, false, false, false, false, true, true>(e, s, a);
+    lift_task(e->cfg.task, [&](auto t) {
+        lift_bools([&](auto c_eta, auto c_nt, auto c_feat, auto c_baked) {
+            constexpr int T = LIFTED(t);
+            constexpr bool ETA = LIFTED(c_eta), NT = LIFTED(c_nt), FEAT = LIFTED(c_feat), BAKED = LIFTED(c_baked);
+#if HG_HELPER > 0
+            // small batches, in-kernel noise: the helper kernel up to resident_envs / HG_HELPER_DIV envs
+            if constexpr (NT && !ETA && !MULTI) if (e->n <= e->resident_envs / HG_HELPER_DIV) {
+                ++e->n_launch[3];
+                launch_kernel(step_help_kernel<T, FEAT, BAKED>, e, s, blocks_for(blocks_for(e->n, 64), HG_HELPER),
+                              128 * HG_HELPER, e->n, a);
                 return;
             }
-            if (feat) eta ? launch_step<T, true, NT, true, MULTI, true>(e, s, a) : launch_step<T, false, NT, true, MULTI, true>(e, s, a);
-            else eta ? launch_step<T, true, NT, false, MULTI, true>(e, s, a) : launch_step<T, false, NT, false, MULTI, true>(e, s, a);
-        } else {
-            if (feat) eta ? launch_step<T, true, NT, true, MULTI, false>(e, s, a) : launch_step<T, false, NT, true, MULTI, false>(e, s, a);
-            else eta ? launch_step<T, true, NT, false, MULTI, false>(e, s, a) : launch_step<T, false, NT, false, MULTI, false>(e, s, a);
-        }
-    };
-    if (e->n <= HG_NT_WAVES * e->resident_envs) pick(std::true_type{});
-    else pick(std::false_type{});
+#endif
+            ++e->n_launch[NT ? 4 : 5];
+            if constexpr (!NT && !MULTI && BAKED) if (nts) {
+                launch_kernel(step_kernel<T, ETA, false, FEAT, false, true, true>, e, s, grid, kStepBlock, e->n, a);
+                return;
+            }
+            launch_kernel(step_kernel<T, ETA, NT, FEAT, MULTI, BAKED, false>, e, s, grid, kStepBlock, e->n, a);
+        }, eta, nt, feat, e->baked);
+    });
     return hipSuccess;
 }
-template <bool MULTI>
-static hipError_t dispatch_task(const hg_env* e, hipStream_t s, const StepArgs& a, bool eta, bool feat) {
-    switch (e->cfg.task) {
-        case HG_TASK_HOVER: return dispatch_step<HG_TASK_HOVER, MULTI>(e, s, a, eta, feat);
-        case HG_TASK_FORWARD_FLIGHT: return dispatch_step<HG_TASK_FORWARD_FLIGHT, MULTI>(e, s, a, eta, feat);
-        default: return dispatch_step<HG_TASK_HELI, MULTI>(e, s, a, eta, feat);
-    }
-}
 
-// hg_rollout_policy's launch: task x injected noise x optional features, the constant-specialised
-// step when the env uses it
-template <int T>
+// hg_rollout_policy's, hg_rollout_ac's and hg_rollout_pop's launches: one-wave blocks of the lone-wave step;
+// task x injected noise (hg_rollout_pop has none) x the optional features x the constant-specialised step.
+// A weather handle's kernels always have the optional features.
 static void launch_rollout_policy(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol, bool eta,
                                   bool feat) {
-    const unsigned grid = (unsigned)((e->n + 63) / 64);
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, STEP_KARGS(e), a, pol); };
+    auto go = [&](auto kern, const auto&... x) { launch_kernel(kern, e, s, blocks_for(e->n, 64), 64, e->n, a, pol, x...); };
     ++e->n_launch[4];
-    if (e->weather) {
-        auto gw = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, STEP_KARGS(e), a, pol, WEATHER_ARG(e));
-        };
-        if (e->baked) eta ? gw(rollout_policy_weather_kernel<T, true, true>) : gw(rollout_policy_weather_kernel<T, false, true>);
-        else eta ? gw(rollout_policy_weather_kernel<T, true, false>) : gw(rollout_policy_weather_kernel<T, false, false>);
-        return;
-    }
-    if (e->baked) {
-        if (feat) eta ? go(rollout_policy_kernel<T, true, true, true>) : go(rollout_policy_kernel<T, false, true, true>);
-        else eta ? go(rollout_policy_kernel<T, true, false, true>) : go(rollout_policy_kernel<T, false, false, true>);
-    } else {
-        if (feat) eta ? go(rollout_policy_kernel<T, true, true, false>) : go(rollout_policy_kernel<T, false, true, false>);
-        else eta ? go(rollout_policy_kernel<T, true, false, false>) : go(rollout_policy_kernel<T, false, false, false>);
-    }
+    lift_task(e->cfg.task, [&](auto t) {
+        if (e->weather)
+            lift_bools([&](auto c_eta, auto c_baked) {
+                go(rollout_policy_weather_kernel<LIFTED(t), LIFTED(c_eta), LIFTED(c_baked)>, weather_args(e));
+            }, eta, e->baked);
+        else
+            lift_bools([&](auto c_eta, auto c_feat, auto c_baked) {
+                go(rollout_policy_kernel<LIFTED(t), LIFTED(c_eta), LIFTED(c_feat), LIFTED(c_baked)>);
+            }, eta, feat, e->baked);
+    });
 }
-// hg_rollout_pop's launch: task x optional features x the constant-specialised step
-template <int T>
-static void launch_rollout_pop(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol, uint32_t tiles,
-                               bool feat) {
-    const unsigned grid = (unsigned)((e->n + 63) / 64);
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, STEP_KARGS(e), a, pol, tiles); };
-    ++e->n_launch[4];
-    if (e->weather) {
-        auto gw = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, STEP_KARGS(e), a, pol, tiles, WEATHER_ARG(e));
-        };
-        e->baked ? gw(rollout_pop_weather_kernel<T, true>) : gw(rollout_pop_weather_kernel<T, false>);
-        return;
-    }
-    if (e->baked) feat ? go(rollout_pop_kernel<T, true, true>) : go(rollout_pop_kernel<T, false, true>);
-    else feat ? go(rollout_pop_kernel<T, true, false>) : go(rollout_pop_kernel<T, false, false>);
-}
-static void dispatch_rollout_pop(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol, uint32_t tiles,
-                                 bool feat) {
-    switch (e->cfg.task) {
-        case HG_TASK_HOVER: launch_rollout_pop<HG_TASK_HOVER>(e, s, a, pol, tiles, feat); break;
-        case HG_TASK_FORWARD_FLIGHT: launch_rollout_pop<HG_TASK_FORWARD_FLIGHT>(e, s, a, pol, tiles, feat); break;
-        default: launch_rollout_pop<HG_TASK_HELI>(e, s, a, pol, tiles, feat); break;
-    }
-}
-// hg_rollout_ac's launch, as hg_rollout_policy's
-template <int T>
 static void launch_rollout_ac(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol, const AcArgs& ac,
                               bool eta, bool feat) {
-    const unsigned grid = (unsigned)((e->n + 63) / 64);
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, STEP_KARGS(e), a, pol, ac); };
+    auto go = [&](auto kern, const auto&... x) { launch_kernel(kern, e, s, blocks_for(e->n, 64), 64, e->n, a, pol, ac, x...); };
     ++e->n_launch[4];
-    if (e->weather) {
-        auto gw = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, STEP_KARGS(e), a, pol, ac, WEATHER_ARG(e));
-        };
-        if (e->baked) eta ? gw(rollout_ac_weather_kernel<T, true, true>) : gw(rollout_ac_weather_kernel<T, false, true>);
-        else eta ? gw(rollout_ac_weather_kernel<T, true, false>) : gw(rollout_ac_weather_kernel<T, false, false>);
-        return;
-    }
-    if (e->baked) {
-        if (feat) eta ? go(rollout_ac_kernel<T, true, true, true>) : go(rollout_ac_kernel<T, false, true, true>);
-        else eta ? go(rollout_ac_kernel<T, true, false, true>) : go(rollout_ac_kernel<T, false, false, true>);
-    } else {
-        if (feat) eta ? go(rollout_ac_kernel<T, true, true, false>) : go(rollout_ac_kernel<T, false, true, false>);
-        else eta ? go(rollout_ac_kernel<T, true, false, false>) : go(rollout_ac_kernel<T, false, false, false>);
-    }
+    lift_task(e->cfg.task, [&](auto t) {
+        if (e->weather)
+            lift_bools([&](auto c_eta, auto c_baked) {
+                go(rollout_ac_weather_kernel<LIFTED(t), LIFTED(c_eta), LIFTED(c_baked)>, weather_args(e));
+            }, eta, e->baked);
+        else
+            lift_bools([&](auto c_eta, auto c_feat, auto c_baked) {
+                go(rollout_ac_kernel<LIFTED(t), LIFTED(c_eta), LIFTED(c_feat), LIFTED(c_baked)>);
+            }, eta, feat, e->baked);
+    });
 }
-static void dispatch_rollout_ac(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol, const AcArgs& ac,
-                                bool eta, bool feat) {
-    switch (e->cfg.task) {
-        case HG_TASK_HOVER: launch_rollout_ac<HG_TASK_HOVER>(e, s, a, pol, ac, eta, feat); break;
-        case HG_TASK_FORWARD_FLIGHT: launch_rollout_ac<HG_TASK_FORWARD_FLIGHT>(e, s, a, pol, ac, eta, feat); break;
-        default: launch_rollout_ac<HG_TASK_HELI>(e, s, a, pol, ac, eta, feat); break;
-    }
-}
-static void dispatch_rollout_policy(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol, bool eta,
-                                    bool feat) {
-    switch (e->cfg.task) {
-        case HG_TASK_HOVER: launch_rollout_policy<HG_TASK_HOVER>(e, s, a, pol, eta, feat); break;
-        case HG_TASK_FORWARD_FLIGHT: launch_rollout_policy<HG_TASK_FORWARD_FLIGHT>(e, s, a, pol, eta, feat); break;
-        default: launch_rollout_policy<HG_TASK_HELI>(e, s, a, pol, eta, feat); break;
-    }
+static void launch_rollout_pop(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol, uint32_t tiles,
+                               bool feat) {
+    auto go = [&](auto kern, const auto&... x) { launch_kernel(kern, e, s, blocks_for(e->n, 64), 64, e->n, a, pol, tiles, x...); };
+    ++e->n_launch[4];
+    lift_task(e->cfg.task, [&](auto t) {
+        if (e->weather)
+            lift_bools([&](auto c_baked) { go(rollout_pop_weather_kernel<LIFTED(t), LIFTED(c_baked)>, weather_args(e)); },
+                       e->baked);
+        else
+            lift_bools([&](auto c_feat, auto c_baked) { go(rollout_pop_kernel<LIFTED(t), LIFTED(c_feat), LIFTED(c_baked)>); },
+                       feat, e->baked);
+    });
 }
 
 // hg_rollout_branch's launch: task x noise mode x the constant-specialised step when the env uses it; the
-// lone-wave variant while the rows fit two waves per SIMD (its registers bound to the one or two waves the
-// rows make), else the bulk one (hg_rollout's rule on rows)
-template <int T>
+// lone-wave step while the rows fit HG_NT_WAVES waves per SIMD, else the bulk one (hg_rollout's rule on rows)
 static void launch_rollout_branch(const hg_env* e, hipStream_t s, const StepArgs& a, const BranchArgs& br, int64_t rows,
                                   bool noise_off) {
-    const unsigned grid = (unsigned)((rows + kStepBlock - 1) / kStepBlock);
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kStepBlock), 0, s, e->state, rows, (uint64_t)e->cfg.seed,
-                           (int64_t)e->cfg.env_offset, PARAM_ARG(e), e->tmpl_dev, a, br);
-    };
-    auto pick = [&](auto waves) {
-        constexpr int W = decltype(waves)::value;
-        if (e->baked) {
-            noise_off ? go(rollout_branch_kernel<T, true, W, true>) : go(rollout_branch_kernel<T, false, W, true>);
-        } else {   // (the generic step fits two waves per SIMD unbound: no WAVES 1 of it)
-            constexpr int WG = W < 2 ? 2 : W;
-            noise_off ? go(rollout_branch_kernel<T, true, WG, false>) : go(rollout_branch_kernel<T, false, WG, false>);
-        }
-    };
-    if (rows <= HG_NT_WAVES * e->resident_envs) {
-        ++e->n_launch[4];
-        if (rows <= e->resident_envs) pick(std::integral_constant<int, 1>{});
-        else pick(std::integral_constant<int, 2>{});
-    } else {
-        ++e->n_launch[5];
-        pick(std::integral_constant<int, 3>{});
-    }
-}
-static void dispatch_rollout_branch(const hg_env* e, hipStream_t s, const StepArgs& a, const BranchArgs& br, int64_t rows,
-                                    bool noise_off) {
-    switch (e->cfg.task) {
-        case HG_TASK_HOVER: launch_rollout_branch<HG_TASK_HOVER>(e, s, a, br, rows, noise_off); break;
-        case HG_TASK_FORWARD_FLIGHT: launch_rollout_branch<HG_TASK_FORWARD_FLIGHT>(e, s, a, br, rows, noise_off); break;
-        default: launch_rollout_branch<HG_TASK_HELI>(e, s, a, br, rows, noise_off); break;
-    }
+    const bool nt = lone_wave(e, rows);
+    // WAVES (rollout_branch_kernel): the lone-wave step's registers bound to the one or two waves per SIMD
+    // the rows make, 3 the bulk step.  The generic step fits two waves per SIMD unbound: no WAVES 1 of it.
+    const bool one = nt && rows <= e->resident_envs && e->baked;
+    ++e->n_launch[nt ? 4 : 5];
+    lift_task(e->cfg.task, [&](auto t) {
+        lift_bools([&](auto c_noise_off, auto c_baked, auto c_nt, auto c_one) {
+            constexpr bool BAKED = LIFTED(c_baked);
+            constexpr int WAVES = !LIFTED(c_nt) ? 3 : (LIFTED(c_one) && BAKED ? 1 : 2);
+            launch_kernel(rollout_branch_kernel<LIFTED(t), LIFTED(c_noise_off), WAVES, BAKED>, e, s,
+                          blocks_for(rows, kStepBlock), kStepBlock, rows, a, br);
+        }, noise_off, e->baked, nt, one);
+    });
 }
 
-// hg_rollout_branch_policy's launch, as hg_rollout_policy's: task x noise mode x the constant-specialised
-// step when the env uses it, one-wave blocks over the rows
-template <int T>
+// hg_rollout_branch_policy's launch: task x noise mode x the constant-specialised step, one-wave blocks of
+// the lone-wave step over the rows
 static void launch_rollout_branch_policy(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol,
                                          const BranchArgs& br, const BranchPolicyArgs& bp, int64_t rows, bool noise_off) {
-    const unsigned grid = (unsigned)((rows + 63) / 64);
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, e->state, rows, (uint64_t)e->cfg.seed,
-                           (int64_t)e->cfg.env_offset, PARAM_ARG(e), e->tmpl_dev, a, pol, br, bp);
-    };
     ++e->n_launch[4];
-    if (e->baked) noise_off ? go(rollout_branch_policy_kernel<T, true, true>) : go(rollout_branch_policy_kernel<T, false, true>);
-    else noise_off ? go(rollout_branch_policy_kernel<T, true, false>) : go(rollout_branch_policy_kernel<T, false, false>);
-}
-static void dispatch_rollout_branch_policy(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol,
-                                           const BranchArgs& br, const BranchPolicyArgs& bp, int64_t rows, bool noise_off) {
-    switch (e->cfg.task) {
-        case HG_TASK_HOVER: launch_rollout_branch_policy<HG_TASK_HOVER>(e, s, a, pol, br, bp, rows, noise_off); break;
-        case HG_TASK_FORWARD_FLIGHT:
-            launch_rollout_branch_policy<HG_TASK_FORWARD_FLIGHT>(e, s, a, pol, br, bp, rows, noise_off);
-            break;
-        default: launch_rollout_branch_policy<HG_TASK_HELI>(e, s, a, pol, br, bp, rows, noise_off); break;
-    }
+    lift_task(e->cfg.task, [&](auto t) {
+        lift_bools([&](auto c_noise_off, auto c_baked) {
+            launch_kernel(rollout_branch_policy_kernel<LIFTED(t), LIFTED(c_noise_off), LIFTED(c_baked)>, e, s,
+                          blocks_for(rows, 64), 64, rows, a, pol, br, bp);
+        }, noise_off, e->baked);
+    });
 }
 
 // ov mode's launch: `ov_trim_blocks` trim blocks (the previous step's ends; blocks without a job exit at
@@ -2588,33 +1475,18 @@ static inline int32_t ov_trim_blocks(int64_t n) {
     b = b < 64 ? 64 : (b > 1024 ? 1024 : b);
     return (int32_t)(b < n ? b : n);
 }
-static void launch_step_ov(const hg_env* e, hipStream_t s, const StepArgs& a, const hgk::RetrimArgs& r) {
-    const int32_t tb = ov_trim_blocks(e->n);
-    const unsigned grid = (unsigned)((e->n + kStepBlock - 1) / kStepBlock) + (unsigned)tb;
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kStepBlock), 0, s, r.count, r.recs, r.T, r.P, STEP_KARGS(e), a, r, tb);
-    };
-    switch (e->cfg.task) {
-        case HG_TASK_HOVER: e->baked ? go(step_ov_kernel<HG_TASK_HOVER, true>) : go(step_ov_kernel<HG_TASK_HOVER, false>); break;
-        case HG_TASK_FORWARD_FLIGHT:
-            e->baked ? go(step_ov_kernel<HG_TASK_FORWARD_FLIGHT, true>) : go(step_ov_kernel<HG_TASK_FORWARD_FLIGHT, false>);
-            break;
-        default: e->baked ? go(step_ov_kernel<HG_TASK_HELI, true>) : go(step_ov_kernel<HG_TASK_HELI, false>); break;
-    }
-}
-
-static void launch_step_fused(const hg_env* e, hipStream_t s, const StepArgs& a, const hgk::RetrimArgs& r, int32_t tb) {
-    const unsigned grid = (unsigned)((e->n + kStepBlock - 1) / kStepBlock) + (unsigned)tb;
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kStepBlock), 0, s, r.count, r.recs, r.T, r.P, STEP_KARGS(e), a, r, tb);
-    };
-    switch (e->cfg.task) {
-        case HG_TASK_HOVER: e->baked ? go(step_fused_kernel<HG_TASK_HOVER, true>) : go(step_fused_kernel<HG_TASK_HOVER, false>); break;
-        case HG_TASK_FORWARD_FLIGHT:
-            e->baked ? go(step_fused_kernel<HG_TASK_FORWARD_FLIGHT, true>) : go(step_fused_kernel<HG_TASK_FORWARD_FLIGHT, false>);
-            break;
-        default: e->baked ? go(step_fused_kernel<HG_TASK_HELI, true>) : go(step_fused_kernel<HG_TASK_HELI, false>); break;
-    }
+// A step with `tb` trim blocks ahead of its own: step_ov_kernel (the previous step's ends), or step_fused_kernel
+// (this step's own resets); the lone-wave step, task x the constant-specialised step
+static void launch_step_trims(const hg_env* e, hipStream_t s, const StepArgs& a, const hgk::RetrimArgs& r, int32_t tb,
+                              bool fused) {
+    const unsigned grid = blocks_for(e->n, kStepBlock) + (unsigned)tb;
+    lift_task(e->cfg.task, [&](auto t) {
+        lift_bools([&](auto c_baked) {
+            const auto kern = fused ? step_fused_kernel<LIFTED(t), LIFTED(c_baked)> : step_ov_kernel<LIFTED(t), LIFTED(c_baked)>;
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(kStepBlock), 0, s, r.count, r.recs, r.T, r.P, e->state, (int64_t)e->n,
+                               (uint64_t)e->cfg.seed, (int64_t)e->cfg.env_offset, PARAM_ARG(e), e->tmpl_dev, a, r, tb);
+        }, e->baked);
+    });
 }
 
 extern "C" {
@@ -3104,7 +1976,7 @@ static int32_t step_impl(hg_env* e, const float* actions, float* obs, float* rew
         r.ov = 1;
         r.tmpl = reinterpret_cast<const float*>(e->tmpl_dev);
         r.tmpl_env = e->Pf.env_templates ? e->tmpl_env : nullptr;
-        launch_step_ov(e, s, a, r);
+        launch_step_trims(e, s, a, r, ov_trim_blocks(e->n), false);
     } else if (fused) {   // this step's resets trimmed in its own launch's first blocks
         ++e->n_launch[1];
 #ifndef HG_FUSED_TB_DIV
@@ -3129,9 +2001,9 @@ static int32_t step_impl(hg_env* e, const float* actions, float* obs, float* rew
         r.claim = e->fused_ring + kFusedSlot * rt_slot + 2;
         r.ctr = reinterpret_cast<const unsigned long long*>(e->fused_ring + kFusedSlot * rt_slot);
         r.nwaves = (int32_t)((e->n + kStepBlock - 1) / kStepBlock);
-        launch_step_fused(e, s, a, r, tb);
+        launch_step_trims(e, s, a, r, tb, true);
     } else {
-        HIP_TRY(dispatch_task<false>(e, s, a, eta != nullptr, feat));
+        HIP_TRY(launch_step<false>(e, s, a, eta != nullptr, feat));
     }
     HIP_TRY(hipGetLastError());
     if (ov) e->ov_chain = key;
@@ -3176,6 +2048,45 @@ int32_t hg_step_rows(hg_env* e, const float* actions, float* obs, float* reward,
                      final_obs_rows, stream);
 }
 
+// The rollouts' prolog.  StepArgs of `nsteps` steps in one launch, with no re-trim queue: the branched
+// rollouts' as it is (they read hmap, actions and nsteps) ...
+static StepArgs rollout_args(const hg_env* e, int32_t nsteps, const float* actions) {
+    StepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.hmap = e->hmap;
+    a.actions = actions;
+    a.nsteps = nsteps;
+    a.retrim_slot = -1;
+    return a;
+}
+// ... and with the per-step outputs [nsteps][N] of the rollouts that step the handle's envs
+static StepArgs rollout_io_args(const hg_env* e, int32_t nsteps, const float* actions, float* obs, float* reward,
+                                uint8_t* terminated, uint8_t* truncated, uint8_t* info, const float* eta) {
+    StepArgs a = rollout_args(e, nsteps, actions);
+    a.obs = obs;
+    a.reward = reward;
+    a.terminated = terminated;
+    a.truncated = truncated;
+    a.info = info;
+    a.eta = eta;
+    a.tmpl_env = e->tmpl_env;
+    // reset_mode RETRIM without auto-reset: every step records its wind, the trim wind of a later
+    // hg_reset (helicopter.py:208-212), as K hg_step calls would
+    a.retrim_wind = e->retrim_wind;
+    return a;
+}
+// whether such a rollout needs the step's optional features (FEAT)
+static bool rollout_feat(const hg_env* e) {
+    return e->Pf.autoreset_next || e->Pf.max_episode_steps != INT32_MAX || e->Pf.env_templates || e->Pf.reset_retrim;
+}
+// a re-trimmed auto-reset needs a launch of the trim between two steps, which a rollout does not have
+static int32_t refuse_retrim_autoreset(const char* who, const hg_env* e) {
+    if (e->Pf.reset_retrim && e->Pf.autoreset)
+        return fail(HG_E_INVALID,
+                    std::string(who) + " does not support auto-resets in reset_mode RETRIM (re-trims run between steps)");
+    return HG_OK;
+}
+
 int32_t hg_rollout(hg_env* e, const float* actions, int32_t nsteps, float* obs, float* reward, uint8_t* terminated,
                    uint8_t* truncated, uint8_t* info, const float* eta, void* stream) {
     if (!e) return fail(HG_E_INVALID, "env is NULL");
@@ -3187,29 +2098,10 @@ int32_t hg_rollout(hg_env* e, const float* actions, int32_t nsteps, float* obs, 
         return fail(HG_E_INVALID, "actions/obs/reward/terminated/truncated must be device pointers");
     if (((uintptr_t)actions & 15) || ((uintptr_t)obs & 15))
         return fail(HG_E_INVALID, "actions and obs must be 16-byte aligned");
-    if (e->Pf.reset_retrim && e->Pf.autoreset)
-        return fail(HG_E_INVALID, "hg_rollout does not support auto-resets in reset_mode RETRIM (re-trims run between steps)");
+    if (refuse_retrim_autoreset("hg_rollout", e) != HG_OK) return HG_E_INVALID;
     e->chain_expect = kChainBroken;
-    StepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.hmap = e->hmap;
-    a.actions = actions;
-    a.obs = obs;
-    a.reward = reward;
-    a.terminated = terminated;
-    a.truncated = truncated;
-    a.info = info;
-    a.eta = eta;
-    a.tmpl_env = e->tmpl_env;
-    a.nsteps = nsteps;
-    a.retrim_slot = -1;
-    // reset_mode RETRIM without auto-reset: every step records its wind, the trim wind of a later
-    // hg_reset (helicopter.py:208-212), as K hg_step calls would
-    a.retrim_wind = e->retrim_wind;
-    hipStream_t s = (hipStream_t)stream;
-    const bool feat = e->Pf.autoreset_next || e->Pf.max_episode_steps != INT32_MAX || e->Pf.env_templates ||
-                      e->Pf.reset_retrim;
-    HIP_TRY(dispatch_task<true>(e, s, a, eta != nullptr, feat));
+    const StepArgs a = rollout_io_args(e, nsteps, actions, obs, reward, terminated, truncated, info, eta);
+    HIP_TRY(launch_step<true>(e, (hipStream_t)stream, a, eta != nullptr, rollout_feat(e)));
     HIP_TRY(hipGetLastError());
     return HG_OK;
 }
@@ -3253,32 +2145,17 @@ int32_t hg_rollout_policy(hg_env* e, const float* obs0, int32_t nsteps, float* a
         return fail(HG_E_INVALID, "obs0/actions_out/obs/reward/terminated/truncated must be device pointers");
     if (((uintptr_t)actions_out & 15) || ((uintptr_t)obs & 15))
         return fail(HG_E_INVALID, "actions_out and obs must be 16-byte aligned");
-    if (e->Pf.reset_retrim && e->Pf.autoreset)
-        return fail(HG_E_INVALID, "hg_rollout_policy does not support auto-resets in reset_mode RETRIM (re-trims run between steps)");
+    if (refuse_retrim_autoreset("hg_rollout_policy", e) != HG_OK) return HG_E_INVALID;
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     e->ov_chain = kChainBroken;   // the next step's pending resets take the serial re-trim
     e->chain_expect = kChainBroken;
-    StepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.hmap = e->hmap;
-    a.obs = obs;
-    a.reward = reward;
-    a.terminated = terminated;
-    a.truncated = truncated;
-    a.info = info;
-    a.eta = eta;
-    a.tmpl_env = e->tmpl_env;
-    a.nsteps = nsteps;
-    a.retrim_slot = -1;
-    a.retrim_wind = e->retrim_wind;   // (reset_mode RETRIM without auto-reset: as hg_rollout)
+    const StepArgs a = rollout_io_args(e, nsteps, nullptr, obs, reward, terminated, truncated, info, eta);
     PolicyArgs pol;
     pol.pk = e->policy_dev;
     pol.obs0 = obs0;
     pol.actions_out = actions_out;
-    const bool feat = e->Pf.autoreset_next || e->Pf.max_episode_steps != INT32_MAX || e->Pf.env_templates ||
-                      e->Pf.reset_retrim;
-    dispatch_rollout_policy(e, (hipStream_t)stream, a, pol, eta != nullptr, feat);
+    launch_rollout_policy(e, (hipStream_t)stream, a, pol, eta != nullptr, rollout_feat(e));
     HIP_TRY(hipGetLastError());
     return HG_OK;
 }
@@ -3325,27 +2202,14 @@ int32_t hg_rollout_ac(hg_env* e, const float* obs0, int32_t nsteps, float* actio
     if ((value != nullptr) != (next_value != nullptr))
         return fail(HG_E_INVALID, "hg_rollout_ac: value and next_value go together (both or neither)");
     if (value && !e->value_set) return fail(HG_E_INVALID, "hg_rollout_ac: values need a value head (hg_set_value_head)");
-    if (e->Pf.reset_retrim && e->Pf.autoreset)
-        return fail(HG_E_INVALID, "hg_rollout_ac does not support auto-resets in reset_mode RETRIM (re-trims run between steps)");
+    if (refuse_retrim_autoreset("hg_rollout_ac", e) != HG_OK) return HG_E_INVALID;
     if (e->Pf.autoreset_next)
         return fail(HG_E_INVALID, "hg_rollout_ac does not support HG_AUTORESET_NEXT_STEP (its filler transitions would need a validity mask)");
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     e->ov_chain = kChainBroken;   // the next step's pending resets take the serial re-trim
     e->chain_expect = kChainBroken;
-    StepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.hmap = e->hmap;
-    a.obs = obs;
-    a.reward = reward;
-    a.terminated = terminated;
-    a.truncated = truncated;
-    a.info = info;
-    a.eta = eta;
-    a.tmpl_env = e->tmpl_env;
-    a.nsteps = nsteps;
-    a.retrim_slot = -1;
-    a.retrim_wind = e->retrim_wind;   // (reset_mode RETRIM without auto-reset: as hg_rollout)
+    const StepArgs a = rollout_io_args(e, nsteps, nullptr, obs, reward, terminated, truncated, info, eta);
     PolicyArgs pol;
     pol.pk = e->policy_dev;
     pol.obs0 = obs0;
@@ -3354,9 +2218,7 @@ int32_t hg_rollout_ac(hg_env* e, const float* obs0, int32_t nsteps, float* actio
     ac.logp = logp;
     ac.value = value;
     ac.next_value = next_value;
-    const bool feat = e->Pf.autoreset_next || e->Pf.max_episode_steps != INT32_MAX || e->Pf.env_templates ||
-                      e->Pf.reset_retrim;
-    dispatch_rollout_ac(e, (hipStream_t)stream, a, pol, ac, eta != nullptr, feat);
+    launch_rollout_ac(e, (hipStream_t)stream, a, pol, ac, eta != nullptr, rollout_feat(e));
     HIP_TRY(hipGetLastError());
     return HG_OK;
 }
@@ -3708,31 +2570,17 @@ int32_t hg_rollout_pop(hg_env* e, const float* images, int64_t P, int64_t envs_p
     if (!e) return fail(HG_E_INVALID, "env is NULL");
     if (!((P - 1) * envs_per_member < e->n && e->n <= P * envs_per_member))
         return fail(HG_E_INVALID, "hg_rollout_pop: need (P - 1) * envs_per_member < num_envs <= P * envs_per_member");
-    if (e->Pf.reset_retrim && e->Pf.autoreset)
-        return fail(HG_E_INVALID, "hg_rollout_pop does not support auto-resets in reset_mode RETRIM (re-trims run between steps)");
+    if (refuse_retrim_autoreset("hg_rollout_pop", e) != HG_OK) return HG_E_INVALID;
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     e->ov_chain = kChainBroken;   // the next step's pending resets take the serial re-trim
     e->chain_expect = kChainBroken;
-    StepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.hmap = e->hmap;
-    a.obs = obs;
-    a.reward = reward;
-    a.terminated = terminated;
-    a.truncated = truncated;
-    a.info = info;
-    a.tmpl_env = e->tmpl_env;
-    a.nsteps = nsteps;
-    a.retrim_slot = -1;
-    a.retrim_wind = e->retrim_wind;   // (reset_mode RETRIM without auto-reset: as hg_rollout)
+    const StepArgs a = rollout_io_args(e, nsteps, nullptr, obs, reward, terminated, truncated, info, nullptr);
     PolicyArgs pol;
     pol.pk = images;
     pol.obs0 = obs0;
     pol.actions_out = actions_out;
-    const bool feat = e->Pf.autoreset_next || e->Pf.max_episode_steps != INT32_MAX || e->Pf.env_templates ||
-                      e->Pf.reset_retrim;
-    dispatch_rollout_pop(e, (hipStream_t)stream, a, pol, (uint32_t)(envs_per_member / 64), feat);
+    launch_rollout_pop(e, (hipStream_t)stream, a, pol, (uint32_t)(envs_per_member / 64), rollout_feat(e));
     HIP_TRY(hipGetLastError());
     return HG_OK;
 }
@@ -3956,19 +2804,14 @@ int32_t hg_rollout_branch(hg_env* e, const float* actions, int32_t horizon, int3
     if (e->weather) return fail(HG_E_INVALID, "hg_rollout_branch does not support per-env weather (hg_set_weather)");
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
-    StepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.hmap = e->hmap;
-    a.actions = actions;
-    a.nsteps = horizon;
-    a.retrim_slot = -1;
+    const StepArgs a = rollout_args(e, horizon, actions);
     BranchArgs br;
     br.ret = ret;
     br.alive_steps = alive_steps;
     br.end_info = end_info;
     br.branches = (uint32_t)branches;
     br.gamma = gamma;
-    dispatch_rollout_branch(e, (hipStream_t)stream, a, br, rows, noise_mode == HG_BRANCH_NOISE_OFF);
+    launch_rollout_branch(e, (hipStream_t)stream, a, br, rows, noise_mode == HG_BRANCH_NOISE_OFF);
     HIP_TRY(hipGetLastError());
     return HG_OK;
 }
@@ -4036,11 +2879,7 @@ int32_t hg_rollout_branch_policy(hg_env* e, const float* obs0, const float* resi
     if (e->weather) return fail(HG_E_INVALID, "hg_rollout_branch_policy does not support per-env weather (hg_set_weather)");
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
-    StepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.hmap = e->hmap;
-    a.nsteps = horizon;
-    a.retrim_slot = -1;
+    const StepArgs a = rollout_args(e, horizon, nullptr);
     PolicyArgs pol;
     pol.pk = e->policy_dev;
     pol.obs0 = obs0;
@@ -4053,7 +2892,7 @@ int32_t hg_rollout_branch_policy(hg_env* e, const float* obs0, const float* resi
     bp.residual = residual;
     bp.bootstrap = bootstrap;
     bp.value_scale = value_scale;
-    dispatch_rollout_branch_policy(e, (hipStream_t)stream, a, pol, br, bp, rows, noise_mode == HG_BRANCH_NOISE_OFF);
+    launch_rollout_branch_policy(e, (hipStream_t)stream, a, pol, br, bp, rows, noise_mode == HG_BRANCH_NOISE_OFF);
     HIP_TRY(hipGetLastError());
     return HG_OK;
 }
@@ -4491,5 +3330,3 @@ int32_t hg_debug_philox(const uint32_t* in, uint32_t* out, int64_t count, void* 
 }
 
 }  // extern "C"
-
-#endif  // HG_RTC
