@@ -39,6 +39,14 @@ using hgk::kCtrCol0;
 using hgk::tix;
 using hgk::AzRec;
 
+namespace hgk {
+// branch_policy_generic.hip: hg_rollout_branch_policy's kernels with the generic constants (fl: a fleet's)
+hipError_t launch_branch_policy_generic(int32_t task, bool noise_off, unsigned grid, hipStream_t s, float* state,
+                                        int64_t rows, uint64_t seed, int64_t envoff, const void* pa, const void* tp,
+                                        const void* step_args, const void* pol, const void* br, const void* bp,
+                                        const void* fl);
+}  // namespace hgk
+
 namespace {
 
 thread_local std::string g_last_error;
@@ -208,6 +216,75 @@ __global__ __launch_bounds__(64, 1) void rollout_branch_policy_kernel(
     x.bp = &bp;
     step_body<TASK, kNT | kFeat | kMulti | kPolicy | kBranch | (NOISE_OFF ? kEta : 0) | (BAKED ? kBaked : 0)>(
         state_p, rows_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, x);
+}
+
+// Mixed fleets (hg_set_fleet): every kernel of the step family once more under a name of its own, with the
+// model constants of the wave's state tile -- `fleet_params`, one scalar load of the tile's class issued
+// before anything else -- where the kernels above pass the handle's one image (`Pa`, unused here; it keeps
+// its place so that one launch path serves every kernel).  step_body's flags are the generic kernels' with
+// the optional features on (a fleet comes with per-env reset templates); never the constant-specialised
+// step, whose literals are one airframe's.
+template <int TASK, bool ETA, bool NT, bool MULTI>
+__global__ __launch_bounds__(kStepBlock, NT ? HG_MIN_WAVES : HG_MIN_WAVES_BULK) void step_fleet_kernel(
+    float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
+    const Template<float>* __restrict__ Tp, const StepArgs a, const FleetArgs fl) {
+    const ParamArg Pc = fleet_params(fl, fleet_wave_tile());
+    step_body<TASK, kFeat | (ETA ? kEta : 0) | (NT ? kNT : 0) | (MULTI ? kMulti : 0)>(state_p, n_p, seed_p, envoff_p, Pc, Tp, a,
+                                                                                      blockIdx.x);
+}
+
+template <int TASK, bool ETA>
+__global__ __launch_bounds__(64, 1) void rollout_policy_fleet_kernel(
+    float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
+    const Template<float>* __restrict__ Tp, const StepArgs a, const PolicyArgs pol, const FleetArgs fl) {
+    const ParamArg Pc = fleet_params(fl, blockIdx.x);
+    StepExtras x;
+    x.pol = &pol;
+    step_body<TASK, kNT | kFeat | kMulti | kPolicy | (ETA ? kEta : 0)>(state_p, n_p, seed_p, envoff_p, Pc, Tp, a, blockIdx.x, x);
+}
+
+template <int TASK, bool ETA>
+__global__ __launch_bounds__(64, 1) void rollout_ac_fleet_kernel(
+    float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
+    const Template<float>* __restrict__ Tp, const StepArgs a, const PolicyArgs pol, const AcArgs ac, const FleetArgs fl) {
+    const ParamArg Pc = fleet_params(fl, blockIdx.x);
+    StepExtras x;
+    x.pol = &pol;
+    x.ac = &ac;
+    step_body<TASK, kNT | kFeat | kMulti | kPolicy | kAc | (ETA ? kEta : 0)>(state_p, n_p, seed_p, envoff_p, Pc, Tp, a,
+                                                                             blockIdx.x, x);
+}
+
+// (a member's tiles and a class's tiles need not coincide: both offsets are the tile's own)
+template <int TASK>
+__global__ __launch_bounds__(64, 1) void rollout_pop_fleet_kernel(
+    float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
+    const Template<float>* __restrict__ Tp, const StepArgs a, const PolicyArgs pol, const uint32_t tiles_per_member,
+    const FleetArgs fl) {
+    const ParamArg Pc = fleet_params(fl, blockIdx.x);
+    PolicyArgs mine = pol;
+    mine.pk = pol.pk + (size_t)(blockIdx.x / tiles_per_member) * hgp::kPolicyFloats;
+    StepExtras x;
+    x.pol = &mine;
+    step_body<TASK, kNT | kFeat | kMulti | kPolicy>(state_p, n_p, seed_p, envoff_p, Pc, Tp, a, blockIdx.x, x);
+}
+
+// The branched rollout: a wave's 64 rows are branches of envs of one state tile -- the host admits only
+// `branches` that divide 64 or are multiples of it -- which is the tile of the wave's first row's env.
+// WAVES 2: the lone-wave step (the generic step fits two waves per SIMD), 3: the bulk step.
+__device__ __forceinline__ uint32_t fleet_branch_tile(uint32_t branches) {
+    return (fleet_wave_tile() * 64u / branches) / (uint32_t)kTileEnvs;   // (rows < 2^31: checked by the host)
+}
+template <int TASK, bool NOISE_OFF, int WAVES>
+__global__ __launch_bounds__(kStepBlock, WAVES) void rollout_branch_fleet_kernel(
+    float* __restrict__ state_p, int64_t rows_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
+    const Template<float>* __restrict__ Tp, const StepArgs a, const BranchArgs br, const FleetArgs fl) {
+    static_assert(WAVES == 2 || WAVES == 3, "WAVES 2: the lone-wave step; 3: the bulk step");
+    const ParamArg Pc = fleet_params(fl, fleet_branch_tile(br.branches));
+    StepExtras x;
+    x.br = &br;
+    step_body<TASK, kFeat | kMulti | kBranch | (NOISE_OFF ? kEta : 0) | (WAVES < 3 ? kNT : 0)>(state_p, rows_p, seed_p, envoff_p,
+                                                                                             Pc, Tp, a, blockIdx.x, x);
 }
 
 // hg_mppi_sample: candidate action sequences around a nominal one, element-wise over [horizon, N*branches]:
@@ -528,12 +605,9 @@ __global__ __launch_bounds__(kBlock) void init_kernel(const Template<float> T, f
 // counter of an env waiting for its next-step reset exported as -1.  The reconstruction replays one
 // add-and-wrap per step since the record's anchor, so the record is re-anchored at the values it
 // returns: a later read replays only the steps taken since this one (bitwise the same values)
-__global__ __launch_bounds__(kBlock) void get_rows_kernel(const uint32_t* tiles, AzRec* az,
-                                                          const Template<float>* T, const float* tmpl_env,
-                                                          const Params<float>* P, uint32_t* state_rows,
-                                                          int32_t* counter_rows, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
+__device__ __forceinline__ void get_rows_env(int64_t i, const uint32_t* tiles, AzRec* az, const Template<float>* T,
+                                             const float* tmpl_env, const Params<float>* P, uint32_t* state_rows,
+                                             int32_t* counter_rows) {
     const int32_t* ctr = reinterpret_cast<const int32_t*>(tiles);
     const int32_t step = ctr[tix(i, kCtrCol0 + 0)], epi = ctr[tix(i, kCtrCol0 + 2)];
     if (state_rows) {
@@ -552,15 +626,30 @@ __global__ __launch_bounds__(kBlock) void get_rows_kernel(const uint32_t* tiles,
     }
 }
 
+__global__ __launch_bounds__(kBlock) void get_rows_kernel(const uint32_t* tiles, AzRec* az,
+                                                          const Template<float>* T, const float* tmpl_env,
+                                                          const Params<float>* P, uint32_t* state_rows,
+                                                          int32_t* counter_rows, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    get_rows_env(i, tiles, az, T, tmpl_env, P, state_rows, counter_rows);
+}
+// ... of a mixed fleet (hg_set_fleet): the azimuth increments f_dpsi_mr / f_dpsi_tr are the env's class's
+__global__ __launch_bounds__(kBlock) void get_rows_fleet_kernel(const uint32_t* tiles, AzRec* az,
+                                                                const Template<float>* T, const float* tmpl_env,
+                                                                const FleetArgs fl, uint32_t* state_rows,
+                                                                int32_t* counter_rows, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    get_rows_env(i, tiles, az, T, tmpl_env, fl.table + fl.tile_class[i / kTileEnvs], state_rows, counter_rows);
+}
+
 // [N, 27] / [N, 3] records -> tiles (set_state; either may be NULL): the azimuth record is rewritten
 // at the env's (new) counters, with the given azimuths or the current ones (both NULL: the
 // azimuths are re-anchored in place, before a reset template changes)
-__global__ __launch_bounds__(kBlock) void set_rows_kernel(uint32_t* tiles, AzRec* az, const Template<float>* T,
-                                                          const float* tmpl_env, const Params<float>* P,
-                                                          const uint32_t* state_rows, const int32_t* counter_rows,
-                                                          int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
+__device__ __forceinline__ void set_rows_env(int64_t i, uint32_t* tiles, AzRec* az, const Template<float>* T,
+                                             const float* tmpl_env, const Params<float>* P, const uint32_t* state_rows,
+                                             const int32_t* counter_rows) {
     int32_t* ctr = reinterpret_cast<int32_t*>(tiles);
     int32_t step = ctr[tix(i, kCtrCol0 + 0)], epi = ctr[tix(i, kCtrCol0 + 2)];
     float2 a;
@@ -581,6 +670,24 @@ __global__ __launch_bounds__(kBlock) void set_rows_kernel(uint32_t* tiles, AzRec
         ctr[tix(i, kCtrCol0 + 2)] = epi;
     }
     az[i] = AzRec{a.x, a.y, hgk::episode_steps(step), epi};
+}
+
+__global__ __launch_bounds__(kBlock) void set_rows_kernel(uint32_t* tiles, AzRec* az, const Template<float>* T,
+                                                          const float* tmpl_env, const Params<float>* P,
+                                                          const uint32_t* state_rows, const int32_t* counter_rows,
+                                                          int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    set_rows_env(i, tiles, az, T, tmpl_env, P, state_rows, counter_rows);
+}
+// ... of a mixed fleet, as get_rows_fleet_kernel
+__global__ __launch_bounds__(kBlock) void set_rows_fleet_kernel(uint32_t* tiles, AzRec* az, const Template<float>* T,
+                                                                const float* tmpl_env, const FleetArgs fl,
+                                                                const uint32_t* state_rows, const int32_t* counter_rows,
+                                                                int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    set_rows_env(i, tiles, az, T, tmpl_env, fl.table + fl.tile_class[i / kTileEnvs], state_rows, counter_rows);
 }
 
 __global__ __launch_bounds__(kBlock) void random_actions_kernel(float* act, int64_t n, int64_t env_offset,
@@ -1159,6 +1266,14 @@ struct hg_env {
     float* wx_rec = nullptr;                // [tiles][2][64] 16-byte words
     float* wx_tep = nullptr;                // [tiles * 64][16]
     std::vector<hg_weather> weather_host;   // [N] while set
+    // mixed fleet (hg_set_fleet): the classes' constant images and each state tile's class, read by the fleet
+    // kernels; the host's copies.  `Pf`, `Pd` and `params_dev` stay the handle's own airframe's.
+    bool fleet = false;
+    Params<float>* fleet_table = nullptr;   // [fleet_cap] device
+    int64_t fleet_cap = 0;
+    int32_t* fleet_tiles = nullptr;         // [tiles] device
+    std::vector<hg_airframe> fleet_af;      // [n_classes] while set
+    std::vector<int32_t> fleet_tile_host;   // [tiles] while set
     float* policy_dev = nullptr;            // the MLP policy's packed image (hg_set_policy, policy_mlp.h)
     bool policy_set = false;
     bool value_set = false;                 // hg_set_value_head was called
@@ -1216,10 +1331,31 @@ static void rederive(hg_env* e) {
 // Upload the fp32 model constants the step kernel reads (after create and every setter).
 // Work already queued on any stream (including non-blocking ones) may still read the constants, so
 // the device is drained first; the copy itself is synchronous.
+// The constant image of a fleet class: derive() of the handle's configuration with the class's airframe, as
+// hg_create would form it for such a handle, per-env reset templates on (a fleet comes with them).
+static Params<float> fleet_image(const hg_env* e, const hg_airframe& af) {
+    hg_config c = e->cfg;
+    c.af = af;
+    Params<float> P = derive<float>(c, e->rows, e->cols);
+    P.env_templates = 1;
+    return P;
+}
+static std::vector<Params<float>> fleet_images(const hg_env* e, const std::vector<hg_airframe>& afs) {
+    std::vector<Params<float>> t;
+    t.reserve(afs.size());
+    for (const hg_airframe& af : afs) t.push_back(fleet_image(e, af));
+    return t;
+}
+static inline FleetArgs fleet_args(const hg_env* e) { return FleetArgs{e->fleet_table, e->fleet_tiles}; }
+
 static int32_t upload_params(hg_env* e) {
     if (!e->params_dev) return HG_OK;
     hipError_t err = hipDeviceSynchronize();
     if (err == hipSuccess) err = hipMemcpy(e->params_dev, &e->Pf, sizeof(e->Pf), hipMemcpyHostToDevice);
+    if (err == hipSuccess && e->fleet) {   // every class's image follows the setters (target, time limits)
+        const std::vector<Params<float>> t = fleet_images(e, e->fleet_af);
+        err = hipMemcpy(e->fleet_table, t.data(), sizeof(Params<float>) * t.size(), hipMemcpyHostToDevice);
+    }
     if (err == hipSuccess && e->pd_dev) err = hipMemcpy(e->pd_dev, &e->Pd, sizeof(e->Pd), hipMemcpyHostToDevice);
     if (err != hipSuccess) return fail(HG_E_HIP, std::string("params upload: ") + hipGetErrorString(err));
     return HG_OK;
@@ -1230,9 +1366,14 @@ static inline unsigned grid_for(int64_t n);
 // the records of episodes begun by an in-kernel reset point at the template).  Synchronous.
 static hipError_t reanchor_azimuths(hg_env* e) {
     if (!e->az) return hipSuccess;
-    hipLaunchKernelGGL(set_rows_kernel, dim3(grid_for(e->n)), dim3(kBlock), 0, 0, reinterpret_cast<uint32_t*>(e->state),
-                       e->az, e->tmpl_dev, e->Pf.env_templates ? e->tmpl_env : nullptr,
-                       (const Params<float>*)e->params_dev, nullptr, nullptr, e->n);
+    if (e->fleet)   // (each env's azimuth increments are its class's)
+        hipLaunchKernelGGL(set_rows_fleet_kernel, dim3(grid_for(e->n)), dim3(kBlock), 0, 0,
+                           reinterpret_cast<uint32_t*>(e->state), e->az, e->tmpl_dev,
+                           e->Pf.env_templates ? e->tmpl_env : nullptr, fleet_args(e), nullptr, nullptr, e->n);
+    else
+        hipLaunchKernelGGL(set_rows_kernel, dim3(grid_for(e->n)), dim3(kBlock), 0, 0, reinterpret_cast<uint32_t*>(e->state),
+                           e->az, e->tmpl_dev, e->Pf.env_templates ? e->tmpl_env : nullptr,
+                           (const Params<float>*)e->params_dev, nullptr, nullptr, e->n);
     hipError_t err = hipGetLastError();
     if (err == hipSuccess) err = hipDeviceSynchronize();
     return err;
@@ -1340,6 +1481,16 @@ static hipError_t launch_step(const hg_env* e, hipStream_t s, const StepArgs& a,
     // next one through the Infinity Cache, plain stores are faster: 37.7 against 38.5 us, 1 M 67.1
     // against 69.4 us)
     const bool nts = !nt && e->n <= HG_NTS_WAVES * e->resident_envs;
+    if (e->fleet) {   // a mixed fleet: kernels of their own, the generic step with the optional features
+        ++e->n_launch[nt ? 4 : 5];
+        lift_task(e->cfg.task, [&](auto t) {
+            lift_bools([&](auto c_eta, auto c_nt) {
+                launch_kernel(step_fleet_kernel<LIFTED(t), LIFTED(c_eta), LIFTED(c_nt), MULTI>, e, s, grid, kStepBlock, e->n, a,
+                              fleet_args(e));
+            }, eta, nt);
+        });
+        return hipSuccess;
+    }
     if (e->weather) {   // per-env weather: kernels of their own, always with the optional features
         ++e->n_launch[nt ? 4 : 5];
         lift_task(e->cfg.task, [&](auto t) {
@@ -1394,7 +1545,9 @@ static void launch_rollout_policy(const hg_env* e, hipStream_t s, const StepArgs
     auto go = [&](auto kern, const auto&... x) { launch_kernel(kern, e, s, blocks_for(e->n, 64), 64, e->n, a, pol, x...); };
     ++e->n_launch[4];
     lift_task(e->cfg.task, [&](auto t) {
-        if (e->weather)
+        if (e->fleet)
+            lift_bools([&](auto c_eta) { go(rollout_policy_fleet_kernel<LIFTED(t), LIFTED(c_eta)>, fleet_args(e)); }, eta);
+        else if (e->weather)
             lift_bools([&](auto c_eta, auto c_baked) {
                 go(rollout_policy_weather_kernel<LIFTED(t), LIFTED(c_eta), LIFTED(c_baked)>, weather_args(e));
             }, eta, e->baked);
@@ -1409,7 +1562,9 @@ static void launch_rollout_ac(const hg_env* e, hipStream_t s, const StepArgs& a,
     auto go = [&](auto kern, const auto&... x) { launch_kernel(kern, e, s, blocks_for(e->n, 64), 64, e->n, a, pol, ac, x...); };
     ++e->n_launch[4];
     lift_task(e->cfg.task, [&](auto t) {
-        if (e->weather)
+        if (e->fleet)
+            lift_bools([&](auto c_eta) { go(rollout_ac_fleet_kernel<LIFTED(t), LIFTED(c_eta)>, fleet_args(e)); }, eta);
+        else if (e->weather)
             lift_bools([&](auto c_eta, auto c_baked) {
                 go(rollout_ac_weather_kernel<LIFTED(t), LIFTED(c_eta), LIFTED(c_baked)>, weather_args(e));
             }, eta, e->baked);
@@ -1424,7 +1579,9 @@ static void launch_rollout_pop(const hg_env* e, hipStream_t s, const StepArgs& a
     auto go = [&](auto kern, const auto&... x) { launch_kernel(kern, e, s, blocks_for(e->n, 64), 64, e->n, a, pol, tiles, x...); };
     ++e->n_launch[4];
     lift_task(e->cfg.task, [&](auto t) {
-        if (e->weather)
+        if (e->fleet)
+            go(rollout_pop_fleet_kernel<LIFTED(t)>, fleet_args(e));
+        else if (e->weather)
             lift_bools([&](auto c_baked) { go(rollout_pop_weather_kernel<LIFTED(t), LIFTED(c_baked)>, weather_args(e)); },
                        e->baked);
         else
@@ -1442,6 +1599,15 @@ static void launch_rollout_branch(const hg_env* e, hipStream_t s, const StepArgs
     // the rows make, 3 the bulk step.  The generic step fits two waves per SIMD unbound: no WAVES 1 of it.
     const bool one = nt && rows <= e->resident_envs && e->baked;
     ++e->n_launch[nt ? 4 : 5];
+    if (e->fleet) {   // a mixed fleet: the generic step's two variants, the constants by the rows' env tile
+        lift_task(e->cfg.task, [&](auto t) {
+            lift_bools([&](auto c_noise_off, auto c_nt) {
+                launch_kernel(rollout_branch_fleet_kernel<LIFTED(t), LIFTED(c_noise_off), LIFTED(c_nt) ? 2 : 3>, e, s,
+                              blocks_for(rows, kStepBlock), kStepBlock, rows, a, br, fleet_args(e));
+            }, noise_off, nt);
+        });
+        return;
+    }
     lift_task(e->cfg.task, [&](auto t) {
         lift_bools([&](auto c_noise_off, auto c_baked, auto c_nt, auto c_one) {
             constexpr bool BAKED = LIFTED(c_baked);
@@ -1452,16 +1618,23 @@ static void launch_rollout_branch(const hg_env* e, hipStream_t s, const StepArgs
     });
 }
 
-// hg_rollout_branch_policy's launch: task x noise mode x the constant-specialised step, one-wave blocks of
-// the lone-wave step over the rows
+// hg_rollout_branch_policy's launch: task x noise mode, one-wave blocks of the lone-wave step over the rows; the
+// constant-specialised step here, the generic one and a fleet's in a translation unit built with other flags
 static void launch_rollout_branch_policy(const hg_env* e, hipStream_t s, const StepArgs& a, const PolicyArgs& pol,
                                          const BranchArgs& br, const BranchPolicyArgs& bp, int64_t rows, bool noise_off) {
     ++e->n_launch[4];
+    if (!e->baked || e->fleet) {   // the generic constants, a fleet's per tile: branch_policy_generic.hip's kernels
+        const FleetArgs fl = fleet_args(e);
+        (void)hgk::launch_branch_policy_generic(e->cfg.task, noise_off, blocks_for(rows, 64), s, e->state, rows,
+                                                (uint64_t)e->cfg.seed, (int64_t)e->cfg.env_offset, PARAM_ARG(e), e->tmpl_dev, &a,
+                                                &pol, &br, &bp, e->fleet ? &fl : nullptr);
+        return;
+    }
     lift_task(e->cfg.task, [&](auto t) {
-        lift_bools([&](auto c_noise_off, auto c_baked) {
-            launch_kernel(rollout_branch_policy_kernel<LIFTED(t), LIFTED(c_noise_off), LIFTED(c_baked)>, e, s,
-                          blocks_for(rows, 64), 64, rows, a, pol, br, bp);
-        }, noise_off, e->baked);
+        lift_bools([&](auto c_noise_off) {
+            launch_kernel(rollout_branch_policy_kernel<LIFTED(t), LIFTED(c_noise_off), true>, e, s, blocks_for(rows, 64), 64,
+                          rows, a, pol, br, bp);
+        }, noise_off);
     });
 }
 
@@ -1599,6 +1772,7 @@ static void release(hg_env* e) {
     dfree(e->trim_block); dfree(e->retrim_wind); dfree(e->retrim_list); dfree(e->retrim_recs);
     dfree(e->ov_recs); dfree(e->ov_ring); dfree(e->fused_ring);
     dfree(e->tmpl_env); dfree(e->setup_batch); dfree(e->policy_dev); dfree(e->wx_rec); dfree(e->wx_tep);
+    dfree(e->fleet_table); dfree(e->fleet_tiles);
     delete e;
 }
 
@@ -1820,6 +1994,8 @@ int32_t hg_set_trim_cond(hg_env* e, const hg_trim_cond* tc) {
     if (!e || !tc) return fail(HG_E_INVALID, "bad env or trim cond");
     if (e->weather)
         return fail(HG_E_INVALID, "hg_set_trim_cond: per-env weather is set; pass the conditions as `conds` to hg_set_weather");
+    if (e->fleet)
+        return fail(HG_E_INVALID, "hg_set_trim_cond: a fleet is set; pass the conditions as `conds` to hg_set_fleet");
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     const hg_trim_cond old = e->cfg.trim;
@@ -2780,6 +2956,14 @@ static int32_t branch_shape(const char* who, int32_t horizon, int32_t branches) 
     if (branches < 1) return fail(HG_E_INVALID, std::string(who) + ": branches must be >= 1");
     return HG_OK;
 }
+// a mixed fleet: the 64 rows of a wave must be branches of envs of one state tile (one class)
+static int32_t fleet_branches(const char* who, const hg_env* e, int32_t branches) {
+    if (e->fleet && 64 % branches != 0 && branches % 64 != 0)
+        return fail(HG_E_INVALID, std::string(who) + ": on a fleet handle (hg_set_fleet) branches must divide 64 or be a "
+                                                      "multiple of 64 (a wave's 64 rows belong to one 64-env tile), got " +
+                                      std::to_string(branches));
+    return HG_OK;
+}
 static int32_t branch_rows(const char* who, const hg_env* e, int32_t branches, int64_t* rows) {
     *rows = e->n * (int64_t)branches;
     if (*rows >= (int64_t)INT32_MAX - 255)
@@ -2802,6 +2986,7 @@ int32_t hg_rollout_branch(hg_env* e, const float* actions, int32_t horizon, int3
     int64_t rows = 0;
     if (branch_rows("hg_rollout_branch", e, branches, &rows) != HG_OK) return HG_E_INVALID;
     if (e->weather) return fail(HG_E_INVALID, "hg_rollout_branch does not support per-env weather (hg_set_weather)");
+    if (fleet_branches("hg_rollout_branch", e, branches) != HG_OK) return HG_E_INVALID;
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     const StepArgs a = rollout_args(e, horizon, actions);
@@ -2877,6 +3062,7 @@ int32_t hg_rollout_branch_policy(hg_env* e, const float* obs0, const float* resi
     int64_t rows = 0;
     if (branch_rows(who, e, branches, &rows) != HG_OK) return HG_E_INVALID;
     if (e->weather) return fail(HG_E_INVALID, "hg_rollout_branch_policy does not support per-env weather (hg_set_weather)");
+    if (fleet_branches(who, e, branches) != HG_OK) return HG_E_INVALID;
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     const StepArgs a = rollout_args(e, horizon, nullptr);
@@ -3050,6 +3236,9 @@ int32_t hg_set_reset_templates(hg_env* e, const float* templates, void* stream) 
     if (e->weather)
         return fail(HG_E_INVALID, "hg_set_reset_templates: per-env weather is set; pass the conditions as `conds` to "
                                   "hg_set_weather (NULL weather reverts)");
+    if (e->fleet)
+        return fail(HG_E_INVALID, "hg_set_reset_templates: a fleet is set; pass the conditions as `conds` to hg_set_fleet "
+                                  "(NULL classes revert)");
     return set_reset_templates(e, templates, stream);
 }
 
@@ -3063,6 +3252,9 @@ int32_t hg_set_weather(hg_env* e, const hg_weather* weather, const hg_trim_cond*
         e->weather_host.clear();
         return set_reset_templates(e, nullptr, stream);
     }
+    if (e->fleet)
+        return fail(HG_E_INVALID, "hg_set_weather: a fleet is set (hg_set_fleet); a fleet together with per-env weather is "
+                                  "not supported");
     if (e->cfg.reset_mode == HG_RESET_RETRIM)
         return fail(HG_E_INVALID, "hg_set_weather: per-env weather needs reset_mode HG_RESET_TEMPLATE (its resets are per-env "
                                   "templates)");
@@ -3171,6 +3363,165 @@ int32_t hg_weather_constants(const hg_config* cfg, const hg_weather* w, float re
     return HG_OK;
 }
 
+// Mixed fleets.  A field of an airframe that is not a finite number (its name for the message), or NULL
+static const char* airframe_nonfinite(const hg_airframe& af) {
+    constexpr size_t kInt = offsetof(hg_airframe, env_TURB_LVL) / sizeof(double);   // the one integer pair
+    static_assert(sizeof(hg_airframe) % sizeof(double) == 0 && offsetof(hg_airframe, env_TURB_LVL) % sizeof(double) == 0,
+                  "hg_airframe is doubles but for env_TURB_LVL and its padding");
+    const double* d = reinterpret_cast<const double*>(&af);
+    for (size_t k = 0; k < sizeof(hg_airframe) / sizeof(double); ++k)
+        if (k != kInt && !std::isfinite(d[k])) return "a non-finite airframe field";
+    return nullptr;
+}
+
+// Host work first (validation, each class's constants and host trim), and only when every class trimmed is
+// anything of the handle replaced: the reset templates (re-anchoring the azimuth records with the constants in
+// use until now), then the class table and the tile map.
+int32_t hg_set_fleet(hg_env* e, const hg_airframe* classes, const hg_trim_cond* conds, int32_t n_classes,
+                     const int32_t* tile_class, int32_t* status_host, void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!classes) {   // back to the handle's own airframe and the shared template
+        if (!e->fleet) return HG_OK;
+        const int32_t rc = set_reset_templates(e, nullptr, stream);   // (re-anchors with the classes' constants)
+        if (rc != HG_OK) return rc;
+        e->fleet = false;
+        e->fleet_af.clear();
+        e->fleet_tile_host.clear();
+        return HG_OK;
+    }
+    const int64_t tiles = (e->n + kTileEnvs - 1) / kTileEnvs;
+    if (n_classes < 1 || n_classes > tiles)
+        return fail(HG_E_INVALID, "hg_set_fleet: n_classes must be in [1, " + std::to_string(tiles) + "] (the handle's 64-env tiles)");
+    if (!tile_class) return fail(HG_E_INVALID, "hg_set_fleet: tile_class is NULL");
+    for (int64_t t = 0; t < tiles; ++t)
+        if (tile_class[t] < 0 || tile_class[t] >= n_classes)
+            return fail(HG_E_INVALID, "hg_set_fleet: tile_class[" + std::to_string(t) + "] = " + std::to_string(tile_class[t]) +
+                                          " is outside [0, n_classes)");
+    if (e->weather)
+        return fail(HG_E_INVALID, "hg_set_fleet: per-env weather is set (hg_set_weather); a fleet together with per-env "
+                                  "weather is not supported");
+    if (e->cfg.reset_mode == HG_RESET_RETRIM)
+        return fail(HG_E_INVALID, "hg_set_fleet: a fleet needs reset_mode HG_RESET_TEMPLATE (the device re-trim reads one "
+                                  "airframe's constants)");
+    const hg_airframe& own = e->cfg.af;
+    for (int32_t c = 0; c < n_classes; ++c) {
+        const hg_airframe& af = classes[c];
+        const std::string who = "hg_set_fleet: class " + std::to_string(c) + ": ";
+        if (const char* why = airframe_nonfinite(af)) return fail(HG_E_INVALID, who + why);
+        if (af.env_TURB_LVL < 0 || af.env_TURB_LVL > 7) return fail(HG_E_INVALID, who + "TURB_LVL must be 0..7");
+        if (af.env_MAX_GR_ALT != own.env_MAX_GR_ALT || af.env_NS_MAX != own.env_NS_MAX || af.env_EW_MAX != own.env_EW_MAX)
+            return fail(HG_E_INVALID, who + "env_MAX_GR_ALT, env_NS_MAX and env_EW_MAX must be the handle's (the terrain is "
+                                            "shared)");
+        if (!gear_layout_ok(fleet_image(e, af)))
+            return fail(HG_E_INVALID, who + "landing gear: the step kernels need the nose wheel on the centre line and the "
+                                            "mains mirrored about it on one waterline");
+    }
+    // each class's trim against its own mean wind, by the code behind hg_trim
+    std::vector<Template<float>> tpl((size_t)n_classes);
+    std::vector<int32_t> status((size_t)n_classes, HG_OK);
+    int32_t nbad = 0, first = -1;
+    std::string first_why;
+    for (int32_t c = 0; c < n_classes; ++c) {
+        hg_config cfg = e->cfg;
+        cfg.af = classes[c];
+        const Params<double> Pd = derive<double>(cfg, e->rows, e->cols);
+        const double W[3] = {Pd.wm[0], Pd.wm[1], Pd.wm[2]};
+        hg_trim_result r;
+        memset(&r, 0, sizeof(r));
+        int32_t rc = do_trim(Pd, e->hmap_host.data(), conds ? conds[c] : e->cfg.trim, W, &r);
+        std::string why = rc != HG_OK ? g_last_error : std::string();
+        if (rc == HG_OK) {   // a search that stopped short of the reference's threshold, or left the numbers
+            bool finite = std::isfinite(r.residual);
+            for (int k = 0; k < 18; ++k) finite = finite && std::isfinite(r.state[k]);
+            for (int k = 0; k < 17; ++k) finite = finite && std::isfinite(r.obs[k]);
+            if (!finite || !(r.residual <= hg::kTrimEps)) {
+                rc = HG_E_TRIM;
+                why = "the trim did not converge (residual " + std::to_string(r.residual) + ")";
+            }
+        }
+        status[(size_t)c] = rc == HG_OK ? HG_OK : HG_E_TRIM;
+        if (rc != HG_OK) {
+            if (first < 0) { first = c; first_why = why; }
+            ++nbad;
+            continue;
+        }
+        Template<float>& t = tpl[(size_t)c];
+        for (int k = 0; k < 18; ++k) t.heli[k] = (float)r.state[k];
+        for (int k = 0; k < 17; ++k) t.obs[k] = (float)r.obs[k];
+        t.carry[0] = (float)r.obs[4];
+        t.carry[1] = (float)r.obs[5];
+        t.carry[2] = (float)r.obs[6];
+        t.carry[3] = (float)r.obs[16];
+    }
+    if (status_host) memcpy(status_host, status.data(), sizeof(int32_t) * (size_t)n_classes);
+    if (nbad)
+        return fail(HG_E_TRIM, "hg_set_fleet: the trim of " + std::to_string(nbad) + " class(es) failed (first: class " +
+                                   std::to_string(first) + ": " + first_why + "); the handle is unchanged");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    // every env's class trim as its reset template
+    std::vector<float> rows((size_t)e->n * kTplFloats);
+    for (int64_t i = 0; i < e->n; ++i)
+        memcpy(&rows[(size_t)i * kTplFloats], &tpl[(size_t)tile_class[i / kTileEnvs]], sizeof(float) * kTplFloats);
+    const std::vector<hg_airframe> afs(classes, classes + n_classes);
+    const std::vector<Params<float>> images = fleet_images(e, afs);
+    float* scratch = nullptr;
+    Params<float>* table = nullptr;
+    auto install = [&]() -> int32_t {
+        HIP_TRY(hipMalloc(&scratch, sizeof(float) * rows.size()));
+        if (n_classes > e->fleet_cap) HIP_TRY(hipMalloc(&table, sizeof(Params<float>) * (size_t)n_classes));
+        if (!e->fleet_tiles) HIP_TRY(hipMalloc(&e->fleet_tiles, sizeof(int32_t) * (size_t)tiles));
+        HIP_TRY(hipMemcpy(scratch, rows.data(), sizeof(float) * rows.size(), hipMemcpyHostToDevice));
+        const int32_t rc = set_reset_templates(e, scratch, stream);   // synchronises; the old constants re-anchor
+        if (rc != HG_OK) return rc;
+        if (table) {
+            dfree(e->fleet_table);
+            e->fleet_table = table;
+            e->fleet_cap = n_classes;
+            table = nullptr;
+        }
+        HIP_TRY(hipMemcpy(e->fleet_table, images.data(), sizeof(Params<float>) * images.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->fleet_tiles, tile_class, sizeof(int32_t) * (size_t)tiles, hipMemcpyHostToDevice));
+        return HG_OK;
+    };
+    const int32_t rc = install();
+    dfree(scratch);
+    dfree(table);
+    if (rc != HG_OK) return rc;
+    e->fleet = true;
+    e->fleet_af = afs;
+    e->fleet_tile_host.assign(tile_class, tile_class + tiles);
+    return HG_OK;
+}
+
+int32_t hg_get_fleet(hg_env* e, int32_t* n_classes, int32_t* tile_class_host, hg_airframe* classes_host,
+                     float* templates_dev) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (!n_classes && !tile_class_host && !classes_host && !templates_dev)
+        return fail(HG_E_INVALID, "hg_get_fleet: nothing to return (every output NULL)");
+    const int64_t tiles = (e->n + kTileEnvs - 1) / kTileEnvs;
+    if (n_classes) *n_classes = e->fleet ? (int32_t)e->fleet_af.size() : 1;
+    if (tile_class_host)
+        for (int64_t t = 0; t < tiles; ++t) tile_class_host[t] = e->fleet ? e->fleet_tile_host[(size_t)t] : 0;
+    if (classes_host) {
+        if (e->fleet) memcpy(classes_host, e->fleet_af.data(), sizeof(hg_airframe) * e->fleet_af.size());
+        else classes_host[0] = e->cfg.af;
+    }
+    if (templates_dev) return hg_get_weather(e, nullptr, templates_dev, nullptr);   // (the templates in use)
+    return HG_OK;
+}
+
+int32_t hg_fleet_constants(const hg_config* cfg, const hg_airframe* af, int32_t rows, int32_t cols, void* out,
+                           int64_t bytes) {
+    if (!cfg || !af || !out || bytes != (int64_t)sizeof(Params<float>))
+        return fail(HG_E_INVALID, "hg_fleet_constants: bad arguments");
+    hg_config c = *cfg;
+    c.af = *af;
+    const Params<float> P = derive<float>(c, rows, cols);
+    memcpy(out, &P, sizeof(P));
+    return HG_OK;
+}
+
 static int32_t set_reset_templates(hg_env* e, const float* templates, void* stream) {
     e->ov_chain = kChainBroken;   // the next step's pending resets take the serial re-trim
     DevGuard dev_guard(e);
@@ -3272,9 +3623,14 @@ int32_t hg_get_state(hg_env* e, float* state, int32_t* counters, void* stream) {
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     if (!state && !counters) return HG_OK;
-    hipLaunchKernelGGL(get_rows_kernel, dim3(grid_for(e->n)), dim3(kBlock), 0, (hipStream_t)stream,
-                       reinterpret_cast<const uint32_t*>(e->state), e->az, e->tmpl_dev,
-                       e->Pf.env_templates ? e->tmpl_env : nullptr, PARAM_ARG(e), (uint32_t*)state, counters, e->n);
+    if (e->fleet)
+        hipLaunchKernelGGL(get_rows_fleet_kernel, dim3(grid_for(e->n)), dim3(kBlock), 0, (hipStream_t)stream,
+                           reinterpret_cast<const uint32_t*>(e->state), e->az, e->tmpl_dev,
+                           e->Pf.env_templates ? e->tmpl_env : nullptr, fleet_args(e), (uint32_t*)state, counters, e->n);
+    else
+        hipLaunchKernelGGL(get_rows_kernel, dim3(grid_for(e->n)), dim3(kBlock), 0, (hipStream_t)stream,
+                           reinterpret_cast<const uint32_t*>(e->state), e->az, e->tmpl_dev,
+                           e->Pf.env_templates ? e->tmpl_env : nullptr, PARAM_ARG(e), (uint32_t*)state, counters, e->n);
     HIP_TRY(hipGetLastError());
     return HG_OK;
 }
@@ -3285,10 +3641,16 @@ int32_t hg_set_state(hg_env* e, const float* state, const int32_t* counters, voi
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     if (!state && !counters) return HG_OK;
-    hipLaunchKernelGGL(set_rows_kernel, dim3(grid_for(e->n)), dim3(kBlock), 0, (hipStream_t)stream,
-                       reinterpret_cast<uint32_t*>(e->state), e->az, e->tmpl_dev,
-                       e->Pf.env_templates ? e->tmpl_env : nullptr, PARAM_ARG(e), (const uint32_t*)state, counters,
-                       e->n);
+    if (e->fleet)
+        hipLaunchKernelGGL(set_rows_fleet_kernel, dim3(grid_for(e->n)), dim3(kBlock), 0, (hipStream_t)stream,
+                           reinterpret_cast<uint32_t*>(e->state), e->az, e->tmpl_dev,
+                           e->Pf.env_templates ? e->tmpl_env : nullptr, fleet_args(e), (const uint32_t*)state, counters,
+                           e->n);
+    else
+        hipLaunchKernelGGL(set_rows_kernel, dim3(grid_for(e->n)), dim3(kBlock), 0, (hipStream_t)stream,
+                           reinterpret_cast<uint32_t*>(e->state), e->az, e->tmpl_dev,
+                           e->Pf.env_templates ? e->tmpl_env : nullptr, PARAM_ARG(e), (const uint32_t*)state, counters,
+                           e->n);
     HIP_TRY(hipGetLastError());
     return HG_OK;
 }

@@ -386,6 +386,28 @@ struct WeatherArgs {
     const float* tep = nullptr;    // [tiles * 64][16] the env's TEP row (13 values), read above 1000 ft only
 };
 
+// hg_set_fleet's airframe classes: a kernel argument of the fleet kernels alone, after every other one -- no
+// existing kernel's argument segment moves.  A state tile (one wave) has one class, so the model constants
+// stay scalar loads from one uniform pointer: step_body is given `table + tile_class[tile]` where the other
+// kernels give it the handle's one image, and is the same code.
+struct FleetArgs {
+    const Params<float>* table = nullptr;   // [n_classes] the classes' constant images
+    const int32_t* tile_class = nullptr;    // [tiles] the class of each 64-env state tile
+};
+// The constants of env tile `tile` (wave-uniform).  One scalar load (constant address space: uniform address,
+// read-only table) in front of every constant load of the wave: the fleet kernels issue it first thing, so it
+// is in flight with the state groups' loads.
+__device__ __forceinline__ ParamArg fleet_params(const FleetArgs& fl, uint32_t tile) {
+    typedef __attribute__((address_space(4))) const int32_t ConstI32;
+    const int32_t c = __builtin_amdgcn_readfirstlane(((ConstI32*)fl.tile_class)[tile]);
+    return fl.table + c;
+}
+// the env tile of this wave of a step-family block (blocks of kStepBlock / 64 tiles)
+__device__ __forceinline__ uint32_t fleet_wave_tile() {
+    if constexpr (kStepBlock == 64) return blockIdx.x;
+    else return blockIdx.x * (kStepBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+}
+
 // What a variant of step_body reads beside StepArgs: a kernel points at the arguments its flags name and
 // leaves the rest at the empty ones, which no code of its variant reads.
 constexpr PolicyArgs kNoPolicy{};

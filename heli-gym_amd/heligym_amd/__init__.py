@@ -12,12 +12,12 @@ from .evolution import ES, es_grad_ref, es_utilities_ref, pop_fitness_ref  # noq
 from .planning import MPPI, PolicyMPPI  # noqa: F401
 from .policy import ActorCriticParams, PPOOptState, bc_loss, ppo_loss  # noqa: F401
 from .stats import RolloutStats, rollout_stats_ref  # noqa: F401
-from .vector import OBS_NAMES, HeliVecEnv, sample_weather  # noqa: F401
+from .vector import OBS_NAMES, HeliVecEnv, sample_fleet, sample_weather  # noqa: F401
 
 __all__ = ["Heli", "HeliHover", "HeliForwardFlight", "HeliVecEnv", "OBS_NAMES", "register_envs",
            "make_vec", "HeliGymError", "MPPI", "PolicyMPPI", "ActorCriticParams", "PPOOptState", "ppo_loss", "bc_loss",
            "RolloutStats", "rollout_stats_ref", "ES", "es_utilities_ref", "es_grad_ref", "pop_fitness_ref",
-           "sample_weather"]
+           "sample_weather", "sample_fleet"]
 
 # gymnasium ids of the reference registry (heligym/__init__.py:4-18) -> task
 ENV_IDS = {"Heli-v0": "heli", "HeliHover-v0": "hover", "HeliForwardFlight-v0": "forward_flight"}

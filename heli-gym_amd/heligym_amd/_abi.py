@@ -205,6 +205,12 @@ _SIGS = {
     "hg_get_weather": (ctypes.c_int32, [_P, ctypes.POINTER(hg_weather), _P, _P]),
     "hg_weather_constants": (ctypes.c_int32, [ctypes.POINTER(hg_config), ctypes.POINTER(hg_weather),
                                               ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
+    "hg_set_fleet": (ctypes.c_int32, [_P, ctypes.POINTER(hg_airframe), ctypes.POINTER(hg_trim_cond), ctypes.c_int32,
+                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), _P]),
+    "hg_get_fleet": (ctypes.c_int32, [_P, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                      ctypes.POINTER(hg_airframe), _P]),
+    "hg_fleet_constants": (ctypes.c_int32, [ctypes.POINTER(hg_config), ctypes.POINTER(hg_airframe), ctypes.c_int32,
+                                            ctypes.c_int32, _P, ctypes.c_int64]),
     "hg_debug_params": (ctypes.c_int32, [ctypes.POINTER(hg_config), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                          _P, ctypes.c_int64]),
     "hg_config_is_baked": (ctypes.c_int32, [ctypes.POINTER(hg_config), ctypes.c_int32, ctypes.c_int32]),

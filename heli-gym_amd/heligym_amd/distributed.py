@@ -21,6 +21,15 @@ def shard_bounds(total, rank, world):
     return offset, count
 
 
+def fleet_shard_tiles(total, offset, count):
+    """[lo, hi) of the global 64-env tiles a shard (offset, count) of `total` envs covers; ValueError unless
+    the shard starts on a tile and ends on one or at the end of the batch."""
+    if offset % 64 != 0 or (count % 64 != 0 and offset + count != total):
+        raise ValueError(f"set_fleet: the shard [{offset}, {offset + count}) of {total} envs is not aligned to the "
+                         "64-env tiles a fleet's classes are given by")
+    return offset // 64, (offset + count + 63) // 64
+
+
 def _staged(t, group):
     """gloo collectives take host tensors: GPU rows go through the host there (the rehearsal of the
     RCCL path on one GPU; RCCL itself moves device memory over xGMI)."""
@@ -83,6 +92,31 @@ class ShardedHeliVecEnv:
 
     def step_async(self, actions, **kw):
         return self.env.step_async(actions, **kw)
+
+    def set_fleet(self, airframes, tile_class=None, **kw):
+        """HeliVecEnv.set_fleet on this rank's shard with its slice of a global `tile_class` (one class per
+        64 consecutive global envs).  Only the classes this shard's tiles use are set on it (a handle holds at
+        most one class per tile); the returned status has the global length, 0 for the others.  The shard's
+        bounds must be tile-aligned: its offset a multiple of 64, and its count too unless it is the last shard."""
+        import numpy as np
+        if airframes is None or tile_class is None:
+            return self.env.set_fleet(airframes, tile_class=tile_class, **kw)
+        lo, hi = fleet_shard_tiles(self.total_envs, self.offset, self.count)
+        tc = tile_class.detach().cpu().numpy() if hasattr(tile_class, "detach") else tile_class
+        if len(tc) != (self.total_envs + 63) // 64:
+            raise ValueError(f"set_fleet: the global tile_class must have {(self.total_envs + 63) // 64} entries, "
+                             f"got {len(tc)}")
+        tc = np.asarray(tc)
+        if tc.dtype.kind not in "iu" or tc.min() < 0 or tc.max() >= len(airframes):
+            raise ValueError(f"set_fleet: tile_class entries must be integers in [0, {len(airframes)})")
+        if kw.get("conds") is not None and len(kw["conds"]) != len(airframes):
+            raise ValueError(f"set_fleet: need {len(airframes)} trim conditions (one per class), got {len(kw['conds'])}")
+        used, local = np.unique(tc[lo:hi], return_inverse=True)
+        if kw.get("conds") is not None:
+            kw["conds"] = [kw["conds"][c] for c in used]
+        status = np.zeros(len(airframes), dtype=np.int32)
+        status[used] = self.env.set_fleet([airframes[c] for c in used], tile_class=local.astype(np.int32), **kw)
+        return status
 
     def gather_obs(self, dst=0):
         return gather_rows(self.env.obs, self.total_envs, dst=dst, group=self.group)

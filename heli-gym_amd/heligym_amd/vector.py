@@ -1567,6 +1567,57 @@ class HeliVecEnv(*_VEC_BASES):
         w = np.frombuffer(arr, dtype=np.float32).reshape(N, 3).copy()
         return {"turb_level": w[:, 0], "wind_dir": w[:, 1], "wind_spd": w[:, 2], "templates": tm}
 
+    def set_fleet(self, airframes, tile_class=None, envs_per_class=None, conds=None):
+        """Mixed fleet (hg_set_fleet): one airframe class per 64-env state tile.  `airframes` is a list of
+        airframe documents or names (anything config.load_airframe takes, sample_fleet's output included);
+        give either `tile_class`, the class of each of the ceil(N/64) tiles, or `envs_per_class`, a multiple of
+        64: consecutive blocks of that many envs take classes 0, 1, ... (every class must get a tile).  Each
+        class is trimmed on the host against its own mean wind -- for conds[c], a trim-condition dict per
+        class, or the env's shared condition -- and its envs reset to that trim from now on.  Returns the
+        per-class trim status (int32 array).  `set_fleet(None)`: back to the env's own airframe and the shared
+        template (returns None).  Raises HeliGymError naming the classes whose trim failed (its `status`
+        attribute holds them all); the env is then as it was.  reset_mode="template" only, not together with
+        set_weather.  Synchronises; call it outside graph capture, step inside as before."""
+        if airframes is None:
+            self._check(self.lib.hg_set_fleet(self._h, None, None, 0, None, None, self._stream()))
+            return None
+        classes, tiles = fleet_arrays(airframes, self.num_envs, tile_class, envs_per_class)
+        C = len(classes)
+        carr = None
+        if conds is not None:
+            if len(conds) != C:
+                raise ValueError(f"set_fleet: need {C} trim conditions (one per class), got {len(conds)}")
+            carr = (_abi.hg_trim_cond * C)()
+            for j, c in enumerate(conds):
+                config.fill_trim(carr[j], c)
+        status = np.full(C, -99, dtype=np.int32)
+        rc = self.lib.hg_set_fleet(self._h, classes, carr, C, tiles.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                   status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self._stream())
+        if rc == -3:   # HG_E_TRIM: name the classes
+            bad = np.nonzero(status != 0)[0]
+            msg = self.lib.hg_last_error()
+            err = _abi.HeliGymError(f"heligym_amd error {rc}: trim failed for classes {bad[:10].tolist()} ({len(bad)} of "
+                                    f"{C}); the fleet was not set ({msg.decode() if msg else ''})")
+            err.status = status
+            raise err
+        self._check(rc)
+        return status
+
+    def get_fleet(self):
+        """dict of `airframes` (a list of {field: value} dicts, one per class; the env's own airframe while no
+        fleet is set), `tile_class` (int32 [ceil(N/64)]) and `templates`, the [N,39] device tensor of reset
+        templates in use."""
+        t, N = self.torch, self.num_envs
+        tiles = (N + 63) // 64
+        n = ctypes.c_int32()
+        self._check(self.lib.hg_get_fleet(self._h, ctypes.byref(n), None, None, None))
+        tc = np.zeros(tiles, dtype=np.int32)
+        arr = (_abi.hg_airframe * n.value)()
+        tm = t.empty((N, 39), dtype=t.float32, device=self.device)
+        self._check(self.lib.hg_get_fleet(self._h, None, tc.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), arr, _ptr(tm)))
+        names = [f for f, _ in _abi.hg_airframe._fields_ if f != "_pad0"]
+        return {"airframes": [{f: getattr(a, f) for f in names} for a in arr], "tile_class": tc, "templates": tm}
+
     def retrim_failures(self):
         """Auto-resets in reset_mode="retrim" whose trim did not converge (they got the template)."""
         c = ctypes.c_int64()
@@ -1614,6 +1665,88 @@ class HeliVecEnv(*_VEC_BASES):
         self._check(self.lib.hg_random_actions(self._h, _ptr(out), int(seed), int(step), float(lo),
                                                float(hi), self._stream()))
         return out
+
+
+def _airframe_fields(af):
+    """The flat {field: value} airframe of a document, a name, or such a dict itself."""
+    if isinstance(af, dict) and "airframe" not in af and "ENV" not in af:
+        return af
+    return config.load_airframe(af)["airframe"]
+
+
+def fleet_arrays(airframes, num_envs, tile_class=None, envs_per_class=None):
+    """set_fleet's inputs checked and packed, before any library call: the (hg_airframe * C) array of the
+    classes and the int32 [ceil(num_envs / 64)] class of each tile."""
+    N = int(num_envs)
+    tiles = (N + 63) // 64
+    if isinstance(airframes, (str, dict)) or not hasattr(airframes, "__len__"):
+        raise ValueError("set_fleet: airframes must be a list of airframe documents or names")
+    C = len(airframes)
+    if C < 1 or C > tiles:
+        raise ValueError(f"set_fleet: need between 1 and {tiles} classes (one per 64-env tile at most), got {C}")
+    if (tile_class is None) == (envs_per_class is None):
+        raise ValueError("set_fleet: give exactly one of tile_class and envs_per_class")
+    if envs_per_class is not None:
+        e = int(envs_per_class)
+        if e != envs_per_class or e < 64 or e % 64 != 0:
+            raise ValueError(f"set_fleet: envs_per_class must be a positive multiple of 64, got {envs_per_class!r}")
+        tc = np.arange(tiles, dtype=np.int64) // (e // 64)
+        if tc[-1] != C - 1:
+            raise ValueError(f"set_fleet: {N} envs in blocks of {e} make {int(tc[-1]) + 1} classes, got {C} airframes")
+    else:
+        tc = np.asarray(tile_class.detach().cpu().numpy() if hasattr(tile_class, "detach") else tile_class)
+        if tc.ndim != 1 or tc.shape[0] != tiles:
+            raise ValueError(f"set_fleet: tile_class must have {tiles} entries (one per 64-env tile), got shape {tc.shape}")
+        if tc.dtype.kind not in "iu":
+            raise ValueError(f"set_fleet: tile_class must be an integer array, got {tc.dtype}")
+        if tc.min() < 0 or tc.max() >= C:
+            raise ValueError(f"set_fleet: tile_class entries must be in [0, {C}), got [{tc.min()}, {tc.max()}]")
+    arr = (_abi.hg_airframe * C)()
+    for j, doc in enumerate(airframes):
+        af = _airframe_fields(doc)
+        for name, _ in _abi.hg_airframe._fields_:
+            if name == "_pad0":
+                continue
+            v = af[name]
+            if name == "env_TURB_LVL":
+                arr[j].env_TURB_LVL = int(v)
+                continue
+            v = float(v)
+            if not np.isfinite(v):
+                raise ValueError(f"set_fleet: class {j}: {name} is not finite ({v})")
+            setattr(arr[j], name, v)
+    return arr, np.ascontiguousarray(tc, dtype=np.int32)
+
+
+FLEET_SPREAD = {"WT": 0.15, "IX": 0.15, "IY": 0.15, "IZ": 0.15, "FS_CG": 0.01, "mr_RPM": 0.03, "tr_RPM": 0.03}
+
+
+def sample_fleet(n_classes, base="aw109", spread=None, seed=0):
+    """n_classes airframe documents around `base` (a name or a document) for HeliVecEnv.set_fleet: each field
+    in `spread` ({field: s}, default FLEET_SPREAD: weight, inertias, CG station, both rotor speeds) is scaled
+    by a uniform factor in [1 - s, 1 + s], a function of `seed` alone (NumPy's default_rng).  Class 0 is `base`
+    itself."""
+    import copy
+    n = int(n_classes)
+    if n < 1:
+        raise ValueError(f"sample_fleet: n_classes must be >= 1, got {n_classes!r}")
+    spread = dict(FLEET_SPREAD if spread is None else spread)
+    doc0 = config.load_airframe(base)
+    for k, s in spread.items():
+        if k not in doc0["airframe"] or k.startswith("env_"):
+            raise ValueError(f"sample_fleet: {k!r} is not an airframe field that can be spread")
+        if not (np.isfinite(s) and 0.0 <= s < 1.0):
+            raise ValueError(f"sample_fleet: spread[{k!r}] must be in [0, 1), got {s!r}")
+    rng = np.random.default_rng(seed)
+    f = rng.random((n, len(spread)))   # drawn for every class, so class c does not depend on n_classes
+    docs = []
+    for c in range(n):
+        doc = copy.deepcopy(doc0)
+        if c > 0:
+            for j, (k, s) in enumerate(spread.items()):
+                doc["airframe"][k] = float(doc0["airframe"][k]) * (1.0 + float(s) * (2.0 * f[c, j] - 1.0))
+        docs.append(doc)
+    return docs
 
 
 def sample_weather(n, turb_level=(0.0, 7.0), wind_spd=(0.0, 40.0), wind_dir=(0.0, 360.0), seed=0):

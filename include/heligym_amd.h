@@ -860,6 +860,52 @@ int32_t hg_get_weather(hg_env* env, hg_weather* out_host, float* templates_dev, 
  * validated for NULL only (no constant of a weather depends on the rest of the configuration today). */
 int32_t hg_weather_constants(const hg_config* cfg, const hg_weather* w, float record[8], float tep_row[16]);
 
+/* ---- Mixed fleets: airframes that differ across one handle's envs, one airframe class per 64-env state tile.
+ *
+ * A handle steps every env with one airframe's constants.  A fleet gives each state tile (envs 64 t .. 64 t + 63,
+ * one wave of the step kernels) a class of its own: the kernels read the tile's class with one scalar load and
+ * take that class's constant image where they took the handle's, so the constants stay scalar loads and the
+ * step's code is the generic step's.  An env of a class steps bitwise like an env of a handle created with that
+ * airframe (same seed, global env id, trim condition).
+ *
+ * classes [n_classes] (host): raw airframe + ENV block of each class.  conds [n_classes] (host) or NULL: the
+ * handle's own trim condition for every class.  tile_class [ceil(N/64)] (host): the class of each 64-env
+ * state tile (envs 64 t .. 64 t + 63).  status_host [n_classes] or NULL: each class's trim status.
+ * classes == NULL: back to the handle's own airframe and the shared reset template.
+ *
+ * Derives each class's constants as hg_create does for a config with that airframe (hg_fleet_constants; dt,
+ * task, target, limits and reset flags are the handle's), trims each class on the host against its own mean
+ * wind (the code behind hg_trim) and installs every env's class trim as its reset template (the code behind
+ * hg_set_reset_templates); env states are not touched.  A trim that fails, does not converge to the
+ * reference's threshold or is not finite: HG_E_TRIM, status_host names the classes, the handle is as it was.
+ * HG_E_INVALID, outputs untouched: a NULL env; n_classes < 1 or > the number of tiles; a tile_class entry
+ * outside [0, n_classes); a non-finite airframe field; a class whose env_MAX_GR_ALT, env_NS_MAX or env_EW_MAX
+ * differs from the handle's (the terrain is shared); reset_mode HG_RESET_RETRIM (the device trim reads one
+ * airframe); a handle with per-env weather set.  A fleet together with per-env weather is out of scope:
+ * hg_set_weather on a fleet handle returns HG_E_INVALID too.
+ * Synchronises with the device; not capturable.  The stepping calls that follow are capturable as before.
+ * Measured at 65 536 hover envs: hg_step 9.10 us with 1 class, 9.03 with 3, 9.10 with 1 024 (one per tile),
+ * against 7.57 for the generic kernel without per-env reset templates; this call 0.055 s for 1 024 classes.
+ * While a fleet is set: hg_step, hg_step_rows, hg_step_chained, hg_rollout, hg_rollout_policy, hg_rollout_ac,
+ * hg_rollout_pop, hg_rollout_branch and hg_rollout_branch_policy step each env with its tile's constants
+ * (kernels of their own: the generic lone-wave and bulk step; never the constant-specialised, run-time
+ * specialised or helper-wave variants), counted by hg_debug_launches in the lone-wave or bulk bucket by the
+ * usual size rule.  The branched rollouts need `branches` to divide 64 or be a multiple of 64 (a wave's 64
+ * rows then belong to one tile), else HG_E_INVALID.  hg_get_state, hg_set_state and hg_reset use each env's
+ * class's rotor speeds for the azimuths.  hg_set_target and hg_set_max_time update every class.
+ * hg_set_trim_cond and hg_set_reset_templates return HG_E_INVALID (pass `conds` here).  hg_trim_batch and
+ * hg_trim_conds_batch keep trimming the handle's own airframe. */
+int32_t hg_set_fleet(hg_env* env, const hg_airframe* classes, const hg_trim_cond* conds, int32_t n_classes,
+                     const int32_t* tile_class, int32_t* status_host, void* stream);
+/* Any output may be NULL (not all).  Without a fleet: one class, the handle's own airframe, every tile 0.
+ * templates_dev [N,39]: the reset templates in use, as hg_get_weather returns them.  Synchronises. */
+int32_t hg_get_fleet(hg_env* env, int32_t* n_classes, int32_t* tile_class_host /* [tiles] or NULL */,
+                     hg_airframe* classes_host /* [n_classes] or NULL */, float* templates_dev /* [N,39] or NULL */);
+/* host only: the Params<float> image of class `af` on a handle configured as `cfg` (its dt, task, target,
+ * limits, reset flags) -- bitwise hg_debug_params of `cfg` with cfg.af replaced by `af`, baked_only = 0 */
+int32_t hg_fleet_constants(const hg_config* cfg, const hg_airframe* af, int32_t rows, int32_t cols,
+                           void* out, int64_t bytes);
+
 /* Run-time specialisation for airframes other than the compiled-in default one (whose constants
  * are instruction literals of the library's step kernel): load a gfx950 code object built from
  * csrc/step_rtc.hip with this env's constant image (`image`, the sizeof(Params<float>) bytes
