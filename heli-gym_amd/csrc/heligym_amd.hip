@@ -1670,6 +1670,13 @@ int hg_debug_timing(void* dst, int64_t bytes) {
 int hg_debug_timing_help(void* dst, int64_t bytes) {
     return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_timing_help), (size_t)bytes) == hipSuccess ? 0 : -1;
 }
+#if HG_TIMING == 2
+// the launch-tail ring (step_kernels.h) and the number of launches recorded so far
+int hg_debug_tail(void* dst, int64_t bytes, uint32_t* launches) {
+    if (hipMemcpyFromSymbol(launches, HIP_SYMBOL(g_tail_launch), sizeof(uint32_t)) != hipSuccess) return -1;
+    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_tail), (size_t)bytes) == hipSuccess ? 0 : -1;
+}
+#endif
 int hg_debug_fused_probe(void* dst, int64_t bytes) {
     return hipMemcpyFromSymbol(dst, HIP_SYMBOL(hgk::g_fused_probe), (size_t)bytes) == hipSuccess ? 0 : -1;
 }

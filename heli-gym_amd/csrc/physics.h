@@ -183,7 +183,12 @@ HD bool wave_any(bool c) {
     return c;
 #endif
 }
-template <typename R> HD R m_sign(R x) { return (R)((x > (R)0) - (x < (R)0)); }
+// sign(x) in R's own domain: 1 with x's sign bit where x compares below or above 0, else +0 (+-0, NaN, and a
+// denormal where compares flush it) -- the value of (R)((x > 0) - (x < 0)) for every input, the same two
+// compares deciding it (one ordered-not-equal compare on the device), without that form's integer
+// subtract-with-borrow and int -> float convert on the reward's dependent chain: compare, bit select, select
+HD float m_sign(float x) { return (x < 0.f || x > 0.f) ? __builtin_copysignf(1.f, x) : 0.f; }
+HD double m_sign(double x) { return (x < 0.0 || x > 0.0) ? __builtin_copysign(1.0, x) : 0.0; }
 template <typename R> HD R m_max(R a, R b) { return a > b ? a : b; }
 
 constexpr double kPi = 3.14159265358979323846;

@@ -255,6 +255,54 @@ HD f2 sincos2(float x) {
     m_sincos(x, &s, &c);
     return f2{s, c};
 }
+// (sin, cos) of two angles at once, sincos2(x.x) and sincos2(x.y): physics.h m_sincos's operation sequence on
+// each element -- the same products, the same explicit fused multiply-adds in the same order, the same
+// quadrant selects -- with the multiplies and multiply-adds written on the pair (v_pk_mul_f32 / v_pk_fma_f32:
+// one issue slot for both angles).  Bitwise the two scalar calls (tests/test_sign_sincos_host.py).
+#ifndef HG_SINCOS_X2   // bit 0: att0, bit 1: att_step's full-sincos branch evaluate phi and psi as one pair (both:
+#define HG_SINCOS_X2 0   // 24 fewer instructions in the lone-wave kernel, but 65 536 envs 6.688 -> 6.825 us per
+#endif                   // step; att0 alone 6.691 -> 6.831, the branch alone 6.678: not adopted, profiles/launch_tail_ab.txt)
+struct SinCos2 {
+    f2 a, b;   // (sin, cos) of x.x, of x.y
+};
+HD f2 splat2(float v) { return f2{v, v}; }
+HD f2 sincos_quadrant(float sr, float cr, float k) {
+    const int q = (int)k;
+    const bool swap = q & 1;
+    const float ss = swap ? cr : sr, cc = swap ? sr : cr;
+    return f2{(q & 2) ? -ss : ss, ((q + 1) & 2) ? -cc : cc};
+}
+HD SinCos2 sincos2x2(f2 x) {
+    const f2 t = x * 0.636619772367581343f;
+    const f2 k = f2{rintf(t.x), rintf(t.y)};
+    f2 r = __builtin_elementwise_fma(k, splat2(-1.57079637050628662109375f), x);
+    r = __builtin_elementwise_fma(k, splat2(4.37113900018624283e-8f), r);
+    r = __builtin_elementwise_fma(k, splat2(1.71512451e-15f), r);
+    const f2 r2 = r * r;
+    f2 sp = __builtin_elementwise_fma(r2, splat2(-1.9515295891e-4f), splat2(8.3321608736e-3f));
+    sp = __builtin_elementwise_fma(r2, sp, splat2(-1.6666654611e-1f));
+    const f2 r3 = r * r2;
+    const f2 sr = __builtin_elementwise_fma(r3, sp, r);
+    f2 cp = __builtin_elementwise_fma(r2, splat2(2.443315711809948e-5f), splat2(-1.388731625493765e-3f));
+    cp = __builtin_elementwise_fma(r2, cp, splat2(4.166664568298827e-2f));
+    cp = __builtin_elementwise_fma(r2, cp, splat2(-0.5f));
+    const f2 cr = __builtin_elementwise_fma(r2, cp, splat2(1.0f));
+    return SinCos2{sincos_quadrant(sr.x, cr.x, k.x), sincos_quadrant(sr.y, cr.y, k.y)};
+}
+// (sin, cos) of phi, theta, psi: phi and psi as one pair (HG_SINCOS_X2), theta scalar
+template <bool X2>
+HD void sincos_att(f2 pp, float th, Att2& a) {
+    if constexpr (X2) {
+        const SinCos2 w = sincos2x2(pp);
+        a.a[0] = w.a;
+        a.a[1] = sincos2(th);
+        a.a[2] = w.b;
+    } else {
+        a.a[0] = sincos2(pp.x);
+        a.a[1] = sincos2(th);
+        a.a[2] = sincos2(pp.y);
+    }
+}
 
 // The step's shared part: controls (:414-422 + the control terms of :226, :281), the density
 // expansion at the committed altitude, the gear-contact bound.
@@ -323,11 +371,7 @@ HD Att2 att_step(const StepK& K, const Att2& a0, f2 pp0, float th0, f2 pp, float
 #ifndef HG_ISA_HOT
     if (wave_any(!in)) {
         HG_STAGE_FLAG(8);
-        if (!in) {
-            a.a[0] = sincos2(pp.x);
-            a.a[1] = sincos2(th);
-            a.a[2] = sincos2(pp.y);
-        }
+        if (!in) sincos_att<(HG_SINCOS_X2 & 2) != 0>(pp, th, a);
     }
 #endif
     return a;
@@ -382,22 +426,17 @@ HD Att2 att_step(const StepK& K, const Att2& a0, f2 pp0, float th0, f2 pp, float
         if (wave_any(!mid)) {
             HG_STAGE_FLAG(8);
             if constexpr (SEL) {
-                const f2 f0 = sincos2(pp.x), f1 = sincos2(th), f2s = sincos2(pp.y);
-                a.a[0] = mid ? a.a[0] : f0;
-                a.a[1] = mid ? a.a[1] : f1;
-                a.a[2] = mid ? a.a[2] : f2s;
+                Att2 f;
+                sincos_att<(HG_SINCOS_X2 & 2) != 0>(pp, th, f);
+                a.a[0] = mid ? a.a[0] : f.a[0];
+                a.a[1] = mid ? a.a[1] : f.a[1];
+                a.a[2] = mid ? a.a[2] : f.a[2];
             } else if (!mid) {
-                a.a[0] = sincos2(pp.x);
-                a.a[1] = sincos2(th);
-                a.a[2] = sincos2(pp.y);
+                sincos_att<(HG_SINCOS_X2 & 2) != 0>(pp, th, a);
             }
         }
 #else
-        if (!small) {
-            a.a[0] = sincos2(pp.x);
-            a.a[1] = sincos2(th);
-            a.a[2] = sincos2(pp.y);
-        }
+        if (!small) sincos_att<(HG_SINCOS_X2 & 2) != 0>(pp, th, a);
 #endif
     }
     return a;
@@ -804,9 +843,7 @@ HD void from_x16(const X16& x, float* s) {   // (s[2], s[3], the rotor azimuths,
 // (sin, cos) of the committed attitude (phi, theta, psi = hs[12], hs[13], hs[14])
 HD Att2 att0(const float* hs) {
     Att2 a0;
-    a0.a[0] = sincos2(hs[12]);
-    a0.a[1] = sincos2(hs[13]);
-    a0.a[2] = sincos2(hs[14]);
+    sincos_att<(HG_SINCOS_X2 & 1) != 0>(f2{hs[12], hs[14]}, hs[13], a0);
     return a0;
 }
 

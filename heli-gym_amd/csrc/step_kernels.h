@@ -138,6 +138,9 @@ constexpr size_t kTplAlloc = 64 * sizeof(float);
 #ifndef HG_TPL_FULL_HELP
 #define HG_TPL_FULL_HELP 1
 #endif
+#ifndef HG_RESET_LDS   // 1: the lone-wave kernels' same-step reset reads the template from the wave's LDS copy
+#define HG_RESET_LDS 1   // under the resetting lanes' mask (0: readlane + select for every lane of the wave)
+#endif
 __device__ __forceinline__ float lane_value(float v, int lane) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
@@ -298,6 +301,30 @@ __device__ __forceinline__ void draw_eta(const StepArgs& a, uint64_t seed, int64
 #define HG_TIMING_WAVES 2048
 #define HG_TIMING_SLOTS 17   // 0..13 phase stamps, 14/15 realtime end/start, 16 the wave's branch flags
 __device__ unsigned long long g_timing[HG_TIMING_WAVES][HG_TIMING_SLOTS];
+__device__ unsigned long long g_timing_help[HG_TIMING_WAVES][5];   // the helper waves' stamps (HSTAMP, below)
+#endif
+#if HG_TIMING == 2
+// HG_TIMING=2, the launch-tail mode: the production schedule (no phase stamps, no wait for the stores), per
+// wave only the realtime stamp at entry, the one after its last store is issued, the branch flags and the
+// hardware ids, for HG_TAIL_RING consecutive launches.  A launch's ring slot is g_tail_launch as the wave
+// reads it at entry; wave 0 advances it as its last act (dependent launches: a launch's waves all enter
+// long before its wave 0 ends; every record carries the index it read, so the reader can check that).
+// The branch flags are plain stores to words of their own (g_timing slots 1..4, zeroed at entry, read back
+// after the end stamp): no load's round trip inside the schedule.
+#define HG_TAIL_RING 128
+#define HG_TAIL_WAVES 1024
+__device__ unsigned long long g_tail[HG_TAIL_RING][HG_TAIL_WAVES][4];   // start, end, flags | launch << 32, HW_ID | XCC_ID << 32
+__device__ unsigned int g_tail_launch;
+#define TSTAMP(j, ...) do { } while (0)
+#define HSTAMP(j, ...) do { } while (0)
+#define HG_STAMP_WAVE() (blockDim.x == 128 ? (int)blockIdx.x : (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6))
+static_assert(HG_STEP_BLOCK != 128, "HG_TIMING builds tell the helper kernel's blocks by their 128 threads");
+#define HG_STAGE_FLAG(bit)                                                                      \
+    do {                                                                                        \
+        const int w_ = HG_STAMP_WAVE();                                                         \
+        if ((threadIdx.x & 63) == 0 && w_ < HG_TAIL_WAVES) g_timing[w_][(bit) == 1 ? 1 : ((bit) == 2 ? 2 : ((bit) == 4 ? 3 : 4))] = (bit); \
+    } while (0)
+#elif HG_TIMING
 #define TSTAMP(j, ...)                                                                          \
     do {                                                                                        \
         asm volatile("" ::__VA_ARGS__);                                                         \
@@ -327,8 +354,7 @@ static_assert(HG_STEP_BLOCK != 128, "HG_TIMING builds tell the helper kernel's b
     } while (0)
 // the small-batch kernel's helper waves (one per tile): 0 start (s_memrealtime), 1 start (s_memtime),
 // 2 the tile's counters arrived (noise key), 3 noise and wind step done, 4 past the hand-off barrier
-__device__ unsigned long long g_timing_help[HG_TIMING_WAVES][5];
-#define HSTAMP(j, ...)                                                                          \
+#define HSTAMP(j, ...)                                                                     \
     do {                                                                                        \
         asm volatile("" ::__VA_ARGS__);                                                         \
         const unsigned long long t_ = __builtin_amdgcn_s_memtime();                             \
@@ -494,6 +520,10 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
     static_assert(!POLICY || kStepBlock == 64, "hg_rollout_policy needs one-wave step blocks (HG_STEP_BLOCK 64)");
     __shared__ float s_obs[(HELP ? HELP * 64 : kStepBlock) * HG_N_OBS];   // one 64-row slice per wave
     __shared__ float s_wind[HELP ? HELP * 8 * 64 : 1];   // HELP: each tile's wind output and wind state
+    // the lone-wave kernels (kNT, the helper kernel): the wave's copy of the reset template, one 256-byte slice
+    // per wave, written at entry from the float each lane loads and read back by the resetting lanes alone
+    constexpr bool kResetLds = HG_RESET_LDS && NT && !MULTI;
+    __shared__ __attribute__((aligned(16))) float s_tpl[kResetLds ? (HELP ? HELP : kStepBlock / 64) * 64 : 4];
     constexpr bool kNTS = NT || NTS;   // non-temporal output stores
     const Params<float>& P0 = *Pa;   // model constants: scalar loads from a device copy
     // BAKED: the default airframe's constants as instruction literals (baked.h); only the runtime
@@ -521,7 +551,12 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
     f32x4* st_b = reinterpret_cast<f32x4*>(state_p + tile * kTileWords) + 4 * kTileEnvs;
 #define GRP(ptr, g) ((ptr) + ((g) - 4) * kTileEnvs)
 
-#if HG_TIMING
+#if HG_TIMING == 2
+    // (the helper kernel's waves are not recorded: the tail mode is the one-wave step's)
+    const unsigned long long tail_t0 = __builtin_amdgcn_s_memrealtime();
+    const unsigned tail_launch = __builtin_amdgcn_readfirstlane(*(volatile unsigned int*)&g_tail_launch);
+    if (HELP == 0 && tid == 0 && tile < HG_TAIL_WAVES) g_timing[tile][1] = g_timing[tile][2] = g_timing[tile][3] = g_timing[tile][4] = 0;
+#elif HG_TIMING
     if ((tid & 63) == 0 && (i >> 6) < HG_TIMING_WAVES) {
         g_timing[i >> 6][15] = __builtin_amdgcn_s_memrealtime();
         g_timing[i >> 6][16] = 0;
@@ -566,6 +601,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
     // (BRANCH: never a reset, no template)
     const float tpl = BRANCH ? 0.f
                              : ((HELP > 0 && HG_TPL_FULL_HELP) || lane < kTplFloats ? reinterpret_cast<const float*>(Tp)[lane] : 0.f);
+    if constexpr (kResetLds) s_tpl[wv * 64 + lane] = tpl;   // (private to the wave: no barrier but the wave's own order)
     // BRANCH: the env this lane's row branches from (rows past the end take row blk0's), and its state
     // groups where its tile keeps them: per-lane 16-byte loads, up to 64 lanes of one address
     uint32_t b_env = 0;
@@ -1011,8 +1047,29 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
 #if HG_TIMING
         HG_STAGE_FLAG(1);
 #endif
-        // Template<float> = heli[18] | carry[4] | obs[17], float c held by lane c.  The readlanes run
-        // in this wave-uniform branch (every lane has loaded its template float), the selects per lane.
+        // Template<float> = heli[18] | carry[4] | obs[17], float c held by lane c.
+        if constexpr (kResetLds) {
+            // the resetting lanes read the wave's LDS copy, ten 16-byte reads of wave-uniform addresses under
+            // their own mask: no lane reads another lane's register, nothing runs for the other lanes
+            __builtin_amdgcn_wave_barrier();
+            if (do_reset) {
+                const f32x4* tq = reinterpret_cast<const f32x4*>(s_tpl + wv * 64);
+                float t[40];
+#pragma unroll
+                for (int q = 0; q < 10; ++q) {
+                    const f32x4 v = tq[q];
+                    t[4 * q] = v.x; t[4 * q + 1] = v.y; t[4 * q + 2] = v.z; t[4 * q + 3] = v.w;
+                }
+#pragma unroll
+                for (int c = 0; c < 18; ++c) hs[c] = t[c];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) carry[c] = t[18 + c];
+#pragma unroll
+                for (int c = 0; c < 17; ++c) obs[c] = t[22 + c];
+            }
+        } else {
+        // The readlanes run in this wave-uniform branch (every lane has loaded its template float), the
+        // selects per lane.
 #pragma unroll
         for (int c = 0; c < 18; ++c) {
             const float v = lane_value(tpl, c);
@@ -1027,6 +1084,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
         for (int c = 0; c < 17; ++c) {
             const float v = lane_value(tpl, 22 + c);
             obs[c] = do_reset ? v : obs[c];
+        }
         }
     }
     if constexpr (NT) {
@@ -1106,7 +1164,25 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
     }
 
     TSTAMP(11, "v"(tid));
-#if HG_TIMING
+#if HG_TIMING == 2
+    if constexpr (HELP == 0 && !MULTI) {
+        // the end stamp once the last store is issued (not drained); then the record, off the measured life
+        asm volatile("" ::: "memory");
+        const unsigned long long tail_t1 = __builtin_amdgcn_s_memrealtime();
+        // HW_ID (register 4: CU_ID bits 11:8, SH_ID 12, SE_ID 15:13) and XCC_ID (register 20, bits 3:0), all 32 bits
+        const unsigned hw = __builtin_amdgcn_s_getreg(4 | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (31 << 11));
+        if (tid == 0 && tile < HG_TAIL_WAVES) {
+            volatile unsigned long long* fl = &g_timing[tile][0];
+            const unsigned long long flags = fl[1] | fl[2] | fl[3] | fl[4];
+            unsigned long long* rec = g_tail[tail_launch % HG_TAIL_RING][tile];
+            rec[0] = tail_t0;
+            rec[1] = tail_t1;
+            rec[2] = flags | ((unsigned long long)tail_launch << 32);
+            rec[3] = hw | ((unsigned long long)xcc << 32);
+            if (tile == 0) g_tail_launch = tail_launch + 1;
+        }
+    }
+#elif HG_TIMING
     __builtin_amdgcn_s_waitcnt(0);
     TSTAMP(12, "v"(tid));
     if ((tid & 63) == 0 && (i >> 6) < HG_TIMING_WAVES) g_timing[i >> 6][14] = __builtin_amdgcn_s_memrealtime();

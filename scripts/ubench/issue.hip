@@ -39,6 +39,24 @@ __global__ void k(float* out, unsigned long long* cyc, int iters) {
             REP8(asm volatile("v_mad_u64_u32 %0, s[0:1], %4, %8, 0\n v_mad_u64_u32 %1, s[0:1], %5, %8, 0\n v_mad_u64_u32 %2, s[0:1], %6, %8, 0\n v_mad_u64_u32 %3, s[0:1], %7, %8, 0"
                          : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3) : "v"(u0), "v"(u1), "v"(u2), "v"(u3), "s"(0xD2511F53u) : "s0", "s1");
                  u0 = (uint32_t)r0 ^ (uint32_t)(r1 >> 32); u1 = (uint32_t)r1; u2 = (uint32_t)r2; u3 = (uint32_t)(r3 >> 32);)
+        } else if (K == 7) {   // a Philox-like round on one dependent chain: v_mul_hi_u32 + v_mul_lo_u32, then the xor
+            uint32_t t;
+            REP8(asm volatile("v_mul_hi_u32 %1, %0, %2\n v_mul_lo_u32 %0, %0, %2\n v_xor_b32 %0, %0, %1"
+                         : "+v"(u0), "=&v"(t) : "s"(0xD2511F53u));)
+        } else if (K == 8) {   // the same round, two independent chains interleaved
+            uint32_t t, s;
+            REP8(asm volatile("v_mul_hi_u32 %2, %0, %4\n v_mul_hi_u32 %3, %1, %4\n v_mul_lo_u32 %0, %0, %4\n v_mul_lo_u32 %1, %1, %4\n"
+                              " v_xor_b32 %0, %0, %2\n v_xor_b32 %1, %1, %3"
+                         : "+v"(u0), "+v"(u1), "=&v"(t), "=&v"(s) : "s"(0xD2511F53u));)
+        } else if (K == 9) {   // the round's two products as one v_mad_u64_u32, one dependent chain
+            uint64_t r;
+            REP8(asm volatile("v_mad_u64_u32 %0, s[0:1], %1, %2, 0" : "=&v"(r) : "v"(u0), "s"(0xD2511F53u) : "s0", "s1");
+                 u0 = (uint32_t)r ^ (uint32_t)(r >> 32);)
+        } else if (K == 10) {   // v_mad_u64_u32 rounds, two independent chains interleaved
+            uint64_t r, q;
+            REP8(asm volatile("v_mad_u64_u32 %0, s[0:1], %2, %4, 0\n v_mad_u64_u32 %1, s[2:3], %3, %4, 0"
+                         : "=&v"(r), "=&v"(q) : "v"(u0), "v"(u1), "s"(0xD2511F53u) : "s0", "s1", "s2", "s3");
+                 u0 = (uint32_t)r ^ (uint32_t)(r >> 32); u1 = (uint32_t)q ^ (uint32_t)(q >> 32);)
         }
     }
     unsigned long long t1 = __builtin_amdgcn_s_memtime();
@@ -76,6 +94,11 @@ int main() {
         run<3>("v_mul_hi_u32", 1, block, grid);
         run<4>("v_sqrt_f32", 1, block, grid);
         run<6>("v_mad_u64_u32 (+xor/mov)", 2, block, grid);
+        // Philox-like rounds (product pair + xor), ticks per round: 8 rounds of each chain per iteration
+        run<7>("mul_hi+mul_lo+xor, 1 chain", 8, block, grid);
+        run<8>("mul_hi+mul_lo+xor, 2 chains", 8, block, grid);
+        run<9>("mad_u64_u32+xor, 1 chain", 8, block, grid);
+        run<10>("mad_u64_u32+xor, 2 chains", 8, block, grid);
     }
     return 0;
 }
