@@ -177,6 +177,77 @@ __global__ __launch_bounds__(64, 1) void rollout_pop_weather_kernel(
                                                                                        blockIdx.x, x);
 }
 
+// Per-env goals (hg_set_goals): the step, the rollout and the two policy rollouts with step_body's GOAL, once
+// more kernels of their own names beside the ones above, for the two tasks with a target.  Always with the
+// optional features, so that per-env reset templates compose with per-env goals.  No helper-wave,
+// non-temporal bulk or run-time specialised variant.  (The branched and the population rollouts refuse a
+// goal handle.)
+template <int TASK, bool ETA, bool NT, bool MULTI, bool BAKED>
+__global__ __launch_bounds__(kStepBlock, NT ? HG_MIN_WAVES : HG_MIN_WAVES_BULK) void step_goal_kernel(
+    float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
+    const Template<float>* __restrict__ Tp, const StepArgs a, const GoalArgs gl) {
+    StepExtras x;
+    x.gl = &gl;
+    step_body<TASK, kFeat | kGoal | (ETA ? kEta : 0) | (NT ? kNT : 0) | (MULTI ? kMulti : 0) | (BAKED ? kBaked : 0)>(
+        state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, x);
+}
+
+template <int TASK, bool ETA, bool BAKED>
+__global__ __launch_bounds__(64, 1) void rollout_policy_goal_kernel(
+    float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
+    const Template<float>* __restrict__ Tp, const StepArgs a, const PolicyArgs pol, const GoalArgs gl) {
+    StepExtras x;
+    x.pol = &pol;
+    x.gl = &gl;
+    step_body<TASK, kNT | kFeat | kMulti | kPolicy | kGoal | (ETA ? kEta : 0) | (BAKED ? kBaked : 0)>(
+        state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, x);
+}
+
+template <int TASK, bool ETA, bool BAKED>
+__global__ __launch_bounds__(64, 1) void rollout_ac_goal_kernel(
+    float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p, ParamArg Pa,
+    const Template<float>* __restrict__ Tp, const StepArgs a, const PolicyArgs pol, const AcArgs ac, const GoalArgs gl) {
+    StepExtras x;
+    x.pol = &pol;
+    x.ac = &ac;
+    x.gl = &gl;
+    step_body<TASK, kNT | kFeat | kMulti | kPolicy | kAc | kGoal | (ETA ? kEta : 0) | (BAKED ? kBaked : 0)>(
+        state_p, n_p, seed_p, envoff_p, Pa, Tp, a, blockIdx.x, x);
+}
+
+// hg_set_goals / hg_reset / hg_set_state on a goal handle, over all N envs.  sample (box mode): every env's
+// record from its counters' episode -- idempotent, the table is a function of the counters.  obs (a relative
+// handle's hg_reset): the rows hg_reset wrote (every row, or the mask's), absolute, into their goal's frame.
+__global__ __launch_bounds__(kBlock) void goal_draw_kernel(const float* __restrict__ state, int64_t n, uint64_t seed,
+                                                           int64_t env_offset, const GoalArgs gl, int32_t task,
+                                                           const uint8_t* __restrict__ mask, float* __restrict__ obs) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    float* rec = reinterpret_cast<float*>(gl.rec + (i / kTileEnvs) * (2 * kTileEnvs) + i % kTileEnvs);   // word 0; word 1 64 words on
+    if (gl.sample) {
+        const int32_t epi = reinterpret_cast<const int32_t*>(state)[tix(i, kCtrCol0 + 2)];
+        float r[hgg::kRecFloats];
+        hgg::goal_draw_record(seed, (uint64_t)(env_offset + i), epi, gl.box, gl.n_x, gl.n_v, r);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            rec[k] = r[k];
+            rec[4 * kTileEnvs + k] = r[4 + k];
+        }
+    }
+    if (obs && gl.relative && (!mask || mask[i])) {
+        const float* g = rec + 4 * kTileEnvs;   // {north, east, sea_alt, vel}
+        float* o = obs + i * 17;
+        if (task == HG_TASK_HOVER) {
+            o[13] -= g[0];
+            o[14] -= g[1];
+            o[15] -= g[2];
+        } else {
+            o[15] -= g[2];
+            o[1] -= g[3];
+        }
+    }
+}
+
 // hg_rollout_branch: the rollout's steps on N * branches rows that start from the N envs' states
 // (step_body's BRANCH).  A wave takes 64 consecutive rows; `rows_p` stands where the step kernels have
 // their env count.  It reads each env's state once, keeps the steps in registers and writes three words
@@ -1274,6 +1345,13 @@ struct hg_env {
     int32_t* fleet_tiles = nullptr;         // [tiles] device
     std::vector<hg_airframe> fleet_af;      // [n_classes] while set
     std::vector<int32_t> fleet_tile_host;   // [tiles] while set
+    // per-env goals (hg_set_goals): the records the goal kernels read and, in box mode, rewrite (goals.h)
+    int32_t goals = HG_GOALS_OFF;           // HG_GOALS_*
+    int32_t goal_obs = HG_GOAL_OBS_ABSOLUTE;
+    float* goal_rec = nullptr;              // [tiles][2][64] 16-byte words
+    std::vector<hg_target> goals_host;      // [N] in table mode
+    hg_goal_box goal_box = {};              // box mode: as given; goal_box32 what the kernels draw from
+    hgg::Box goal_box32 = {};
     float* policy_dev = nullptr;            // the MLP policy's packed image (hg_set_policy, policy_mlp.h)
     bool policy_set = false;
     bool value_set = false;                 // hg_set_value_head was called
@@ -1460,6 +1538,21 @@ static inline unsigned blocks_for(int64_t n, int block) { return (unsigned)((n +
 static inline WeatherArgs weather_args(const hg_env* e) {
     return WeatherArgs{reinterpret_cast<const f32x4*>(e->wx_rec), e->wx_tep};
 }
+static inline GoalArgs goal_args(const hg_env* e) {
+    GoalArgs g;
+    g.rec = reinterpret_cast<f32x4*>(e->goal_rec);
+    g.box = e->goal_box32;
+    hgg::goal_norms(e->cfg.af, &g.n_x, &g.n_v);
+    g.sample = e->goals == HG_GOALS_BOX ? 1 : 0;
+    g.relative = e->goal_obs == HG_GOAL_OBS_RELATIVE ? 1 : 0;
+    return g;
+}
+// the two tasks with a target (a goal handle has one of them)
+template <typename F>
+static auto lift_goal_task(int32_t task, F&& f) {
+    if (task == HG_TASK_HOVER) return f(std::integral_constant<int, HG_TASK_HOVER>{});
+    return f(std::integral_constant<int, HG_TASK_FORWARD_FLIGHT>{});
+}
 // The lone-wave (NT) step while a launch's envs or rows fit HG_NT_WAVES waves per SIMD, past it the bulk step
 static inline bool lone_wave(const hg_env* e, int64_t n) { return n <= HG_NT_WAVES * e->resident_envs; }
 
@@ -1497,6 +1590,16 @@ static hipError_t launch_step(const hg_env* e, hipStream_t s, const StepArgs& a,
             lift_bools([&](auto c_eta, auto c_nt, auto c_baked) {
                 launch_kernel(step_weather_kernel<LIFTED(t), LIFTED(c_eta), LIFTED(c_nt), MULTI, LIFTED(c_baked)>, e, s, grid,
                               kStepBlock, e->n, a, weather_args(e));
+            }, eta, nt, e->baked);
+        });
+        return hipSuccess;
+    }
+    if (e->goals) {   // per-env goals: kernels of their own, always with the optional features
+        ++e->n_launch[nt ? 4 : 5];
+        lift_goal_task(e->cfg.task, [&](auto t) {
+            lift_bools([&](auto c_eta, auto c_nt, auto c_baked) {
+                launch_kernel(step_goal_kernel<LIFTED(t), LIFTED(c_eta), LIFTED(c_nt), MULTI, LIFTED(c_baked)>, e, s, grid,
+                              kStepBlock, e->n, a, goal_args(e));
             }, eta, nt, e->baked);
         });
         return hipSuccess;
@@ -1544,6 +1647,14 @@ static void launch_rollout_policy(const hg_env* e, hipStream_t s, const StepArgs
                                   bool feat) {
     auto go = [&](auto kern, const auto&... x) { launch_kernel(kern, e, s, blocks_for(e->n, 64), 64, e->n, a, pol, x...); };
     ++e->n_launch[4];
+    if (e->goals) {
+        lift_goal_task(e->cfg.task, [&](auto t) {
+            lift_bools([&](auto c_eta, auto c_baked) {
+                go(rollout_policy_goal_kernel<LIFTED(t), LIFTED(c_eta), LIFTED(c_baked)>, goal_args(e));
+            }, eta, e->baked);
+        });
+        return;
+    }
     lift_task(e->cfg.task, [&](auto t) {
         if (e->fleet)
             lift_bools([&](auto c_eta) { go(rollout_policy_fleet_kernel<LIFTED(t), LIFTED(c_eta)>, fleet_args(e)); }, eta);
@@ -1561,6 +1672,14 @@ static void launch_rollout_ac(const hg_env* e, hipStream_t s, const StepArgs& a,
                               bool eta, bool feat) {
     auto go = [&](auto kern, const auto&... x) { launch_kernel(kern, e, s, blocks_for(e->n, 64), 64, e->n, a, pol, ac, x...); };
     ++e->n_launch[4];
+    if (e->goals) {
+        lift_goal_task(e->cfg.task, [&](auto t) {
+            lift_bools([&](auto c_eta, auto c_baked) {
+                go(rollout_ac_goal_kernel<LIFTED(t), LIFTED(c_eta), LIFTED(c_baked)>, goal_args(e));
+            }, eta, e->baked);
+        });
+        return;
+    }
     lift_task(e->cfg.task, [&](auto t) {
         if (e->fleet)
             lift_bools([&](auto c_eta) { go(rollout_ac_fleet_kernel<LIFTED(t), LIFTED(c_eta)>, fleet_args(e)); }, eta);
@@ -1779,6 +1898,7 @@ static void release(hg_env* e) {
     dfree(e->trim_block); dfree(e->retrim_wind); dfree(e->retrim_list); dfree(e->retrim_recs);
     dfree(e->ov_recs); dfree(e->ov_ring); dfree(e->fused_ring);
     dfree(e->tmpl_env); dfree(e->setup_batch); dfree(e->policy_dev); dfree(e->wx_rec); dfree(e->wx_tep);
+    dfree(e->goal_rec);
     dfree(e->fleet_table); dfree(e->fleet_tiles);
     delete e;
 }
@@ -1990,6 +2110,7 @@ int32_t hg_load_specialized(hg_env* e, const char* code_object, int32_t task, co
 
 int32_t hg_set_target(hg_env* e, const hg_target* t) {
     if (!e || !t) return fail(HG_E_INVALID, "bad env or target");
+    if (e->goals) return fail(HG_E_INVALID, "hg_set_target: per-env goals are set; pass goals to hg_set_goals (both NULL reverts)");
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     e->cfg.target = *t;
@@ -2017,6 +2138,8 @@ int32_t hg_get_template(const hg_env* e, hg_trim_result* out) {
     *out = e->trim;
     return HG_OK;
 }
+
+static int32_t goal_redraw(hg_env* e, hipStream_t s, const uint8_t* mask, float* obs);
 
 int32_t hg_reset(hg_env* e, const uint8_t* mask, float* obs, void* stream) {
     if (!e) return fail(HG_E_INVALID, "env is NULL");
@@ -2050,7 +2173,7 @@ int32_t hg_reset(hg_env* e, const uint8_t* mask, float* obs, void* stream) {
         HIP_TRY(hgk::launch_retrim(r, retrim_grid(e->n), s));
         HIP_TRY(hipGetLastError());
     }
-    return HG_OK;
+    return goal_redraw(e, s, mask, obs);   // (a goal handle: the new episodes' goals, the rows in their frame)
 }
 
 static int32_t step_impl(hg_env* e, const float* actions, float* obs, float* reward, uint8_t* terminated,
@@ -2753,6 +2876,7 @@ int32_t hg_rollout_pop(hg_env* e, const float* images, int64_t P, int64_t envs_p
     if (!e) return fail(HG_E_INVALID, "env is NULL");
     if (!((P - 1) * envs_per_member < e->n && e->n <= P * envs_per_member))
         return fail(HG_E_INVALID, "hg_rollout_pop: need (P - 1) * envs_per_member < num_envs <= P * envs_per_member");
+    if (e->goals) return fail(HG_E_INVALID, "hg_rollout_pop does not support per-env goals (hg_set_goals): its members are compared on one task");
     if (refuse_retrim_autoreset("hg_rollout_pop", e) != HG_OK) return HG_E_INVALID;
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
@@ -2993,6 +3117,7 @@ int32_t hg_rollout_branch(hg_env* e, const float* actions, int32_t horizon, int3
     int64_t rows = 0;
     if (branch_rows("hg_rollout_branch", e, branches, &rows) != HG_OK) return HG_E_INVALID;
     if (e->weather) return fail(HG_E_INVALID, "hg_rollout_branch does not support per-env weather (hg_set_weather)");
+    if (e->goals) return fail(HG_E_INVALID, "hg_rollout_branch does not support per-env goals (hg_set_goals): a branch's rows share no goal record");
     if (fleet_branches("hg_rollout_branch", e, branches) != HG_OK) return HG_E_INVALID;
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
@@ -3069,6 +3194,7 @@ int32_t hg_rollout_branch_policy(hg_env* e, const float* obs0, const float* resi
     int64_t rows = 0;
     if (branch_rows(who, e, branches, &rows) != HG_OK) return HG_E_INVALID;
     if (e->weather) return fail(HG_E_INVALID, "hg_rollout_branch_policy does not support per-env weather (hg_set_weather)");
+    if (e->goals) return fail(HG_E_INVALID, "hg_rollout_branch_policy does not support per-env goals (hg_set_goals): a branch's rows share no goal record");
     if (fleet_branches(who, e, branches) != HG_OK) return HG_E_INVALID;
     DevGuard dev_guard(e);
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
@@ -3262,6 +3388,9 @@ int32_t hg_set_weather(hg_env* e, const hg_weather* weather, const hg_trim_cond*
     if (e->fleet)
         return fail(HG_E_INVALID, "hg_set_weather: a fleet is set (hg_set_fleet); a fleet together with per-env weather is "
                                   "not supported");
+    if (e->goals)
+        return fail(HG_E_INVALID, "hg_set_weather: per-env goals are set (hg_set_goals); goals together with per-env weather "
+                                  "are not supported");
     if (e->cfg.reset_mode == HG_RESET_RETRIM)
         return fail(HG_E_INVALID, "hg_set_weather: per-env weather needs reset_mode HG_RESET_TEMPLATE (its resets are per-env "
                                   "templates)");
@@ -3370,6 +3499,168 @@ int32_t hg_weather_constants(const hg_config* cfg, const hg_weather* w, float re
     return HG_OK;
 }
 
+// Per-env goals.  The fields of a goal the task does not use are the handle's target's.
+static hg_target goal_filled(int32_t task, const hg_target& g, const hg_target& own) {
+    hg_target t = own;
+    t.sea_alt = g.sea_alt;
+    if (task == HG_TASK_HOVER) {
+        t.north_loc = g.north_loc;
+        t.east_loc = g.east_loc;
+    } else {
+        t.vel = g.vel;
+    }
+    return t;
+}
+static void goal_record_of(const hg_config& c, const hg_target& t, float rec[hgg::kRecFloats]) {
+    double n_x, n_v, g[4];
+    hgg::goal_norms(c.af, &n_x, &n_v);
+    hgg::target_fields(t, g);
+    hgg::goal_record(g, n_x, n_v, rec);
+}
+// (the handle's device is current) box mode: every env's record from its counters; `obs`: a relative handle's
+// hg_reset rows into their goal's frame.  Nothing to do for a handle without goals.
+static int32_t goal_redraw(hg_env* e, hipStream_t s, const uint8_t* mask, float* obs) {
+    if (!e->goals) return HG_OK;
+    const bool shift = obs && e->goal_obs == HG_GOAL_OBS_RELATIVE;
+    if (e->goals != HG_GOALS_BOX && !shift) return HG_OK;
+    hipLaunchKernelGGL(goal_draw_kernel, dim3(grid_for(e->n)), dim3(kBlock), 0, s, e->state, e->n, (uint64_t)e->cfg.seed,
+                       (int64_t)e->cfg.env_offset, goal_args(e), e->cfg.task, mask, shift ? obs : nullptr);
+    HIP_TRY(hipGetLastError());
+    return HG_OK;
+}
+
+int32_t hg_set_goals(hg_env* e, const hg_target* goals, const hg_goal_box* box, int32_t obs_mode, void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (goals && box) return fail(HG_E_INVALID, "hg_set_goals: both goals and box given (a table or a box, not both)");
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    if (!goals && !box) {   // back to the handle-wide target
+        if (!e->goals) return HG_OK;
+        HIP_TRY(hipDeviceSynchronize());
+        e->goals = HG_GOALS_OFF;
+        e->goal_obs = HG_GOAL_OBS_ABSOLUTE;
+        e->goals_host.clear();
+        return HG_OK;
+    }
+    const int32_t task = e->cfg.task;
+    if (task != HG_TASK_HOVER && task != HG_TASK_FORWARD_FLIGHT)
+        return fail(HG_E_INVALID, "hg_set_goals: HG_TASK_HELI has no target");
+    if (obs_mode != HG_GOAL_OBS_ABSOLUTE && obs_mode != HG_GOAL_OBS_RELATIVE)
+        return fail(HG_E_INVALID, "hg_set_goals: obs_mode must be HG_GOAL_OBS_ABSOLUTE or HG_GOAL_OBS_RELATIVE");
+    if (e->cfg.reset_mode == HG_RESET_RETRIM)
+        return fail(HG_E_INVALID, "hg_set_goals: per-env goals need reset_mode HG_RESET_TEMPLATE (the trim kernel writes the "
+                                  "observation rows)");
+    if (e->weather)
+        return fail(HG_E_INVALID, "hg_set_goals: per-env weather is set (hg_set_weather); goals together with per-env weather "
+                                  "are not supported");
+    if (e->fleet)
+        return fail(HG_E_INVALID, "hg_set_goals: a fleet is set (hg_set_fleet); goals together with a fleet are not supported");
+    const int64_t n = e->n, np = hgg::padded_envs(n);
+    std::vector<float> rec((size_t)np * hgg::kRecFloats, 0.f);
+    std::vector<hg_target> filled;
+    if (goals) {
+        filled.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i) {
+            const char* bad = hgg::check_target(task, goals[i]);
+            if (bad) return fail(HG_E_INVALID, "hg_set_goals: env " + std::to_string(i) + ": " + bad);
+            filled[(size_t)i] = goal_filled(task, goals[i], e->cfg.target);
+        }
+    } else {
+        const char* bad = hgg::check_box(task, *box);
+        if (bad) return fail(HG_E_INVALID, std::string("hg_set_goals: box: ") + bad);
+    }
+    for (int64_t i = 0; i < np; ++i) {   // (box mode and the padding of a ragged last tile: the handle's target)
+        float r[hgg::kRecFloats];
+        goal_record_of(e->cfg, goals && i < n ? filled[(size_t)i] : e->cfg.target, r);
+        for (int k = 0; k < 4; ++k) {
+            rec[hgg::rec_index(i, 0, k)] = r[k];
+            rec[hgg::rec_index(i, 1, k)] = r[4 + k];
+        }
+    }
+    HIP_TRY(hipDeviceSynchronize());   // queued steps may still read the records being replaced
+    if (!e->goal_rec) HIP_TRY(hipMalloc(&e->goal_rec, sizeof(float) * rec.size()));
+    HIP_TRY(hipMemcpy(e->goal_rec, rec.data(), sizeof(float) * rec.size(), hipMemcpyHostToDevice));
+    e->goals = goals ? HG_GOALS_TABLE : HG_GOALS_BOX;
+    e->goal_obs = obs_mode;
+    e->goals_host.swap(filled);
+    e->goal_box = hg_goal_box{};
+    e->goal_box32 = hgg::Box{};
+    e->ov_chain = kChainBroken;
+    e->chain_expect = kChainBroken;
+    if (box) {
+        e->goal_box.lo = goal_filled(task, box->lo, e->cfg.target);
+        e->goal_box.hi = goal_filled(task, box->hi, e->cfg.target);
+        e->goal_box32 = hgg::make_box(task, *box, e->cfg.target);
+        const int32_t rc = goal_redraw(e, (hipStream_t)stream, nullptr, nullptr);
+        if (rc != HG_OK) return rc;
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    }
+    return HG_OK;
+}
+
+int32_t hg_get_goals(hg_env* e, hg_target* goals, hg_goal_box* box, int32_t* mode, int32_t* obs_mode, void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (mode) *mode = e->goals;
+    if (obs_mode) *obs_mode = e->goal_obs;
+    if (box) *box = e->goals == HG_GOALS_BOX ? e->goal_box : hg_goal_box{};
+    if (!goals) return HG_OK;
+    if (e->goals != HG_GOALS_BOX) {
+        for (int64_t i = 0; i < e->n; ++i) goals[i] = e->goals ? e->goals_host[(size_t)i] : e->cfg.target;
+        return HG_OK;
+    }
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    std::vector<float> rec((size_t)hgg::padded_envs(e->n) * hgg::kRecFloats);
+    HIP_TRY(hipMemcpyAsync(rec.data(), e->goal_rec, sizeof(float) * rec.size(), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    for (int64_t i = 0; i < e->n; ++i) {
+        hg_target t = e->cfg.target;   // (heading, and the fields the task does not use)
+        t.sea_alt = rec[hgg::rec_index(i, 1, 2)];
+        if (e->cfg.task == HG_TASK_HOVER) {
+            t.north_loc = rec[hgg::rec_index(i, 1, 0)];
+            t.east_loc = rec[hgg::rec_index(i, 1, 1)];
+        } else {
+            t.vel = rec[hgg::rec_index(i, 1, 3)];
+        }
+        goals[i] = t;
+    }
+    return HG_OK;
+}
+
+int32_t hg_goal_record(const hg_config* cfg, const hg_target* target, float rec[8]) {
+    if (!cfg || !target || !rec) return fail(HG_E_INVALID, "hg_goal_record: NULL argument");
+    goal_record_of(*cfg, *target, rec);
+    return HG_OK;
+}
+
+int32_t hg_goal_draw(const hg_config* cfg, const hg_goal_box* box, int64_t global_env, int32_t episode, hg_target* out,
+                     float rec[8]) {
+    if (!cfg || !box) return fail(HG_E_INVALID, "hg_goal_draw: NULL argument");
+    if (!out && !rec) return fail(HG_E_INVALID, "hg_goal_draw: nothing to return (both outputs NULL)");
+    if (cfg->task != HG_TASK_HOVER && cfg->task != HG_TASK_FORWARD_FLIGHT)
+        return fail(HG_E_INVALID, "hg_goal_draw: HG_TASK_HELI has no target");
+    const char* bad = hgg::check_box(cfg->task, *box);
+    if (bad) return fail(HG_E_INVALID, std::string("hg_goal_draw: box: ") + bad);
+    const hgg::Box b = hgg::make_box(cfg->task, *box, cfg->target);
+    double n_x, n_v;
+    hgg::goal_norms(cfg->af, &n_x, &n_v);
+    float r[hgg::kRecFloats];
+    hgg::goal_draw_record((uint64_t)cfg->seed, (uint64_t)global_env, episode, b, n_x, n_v, r);
+    if (rec) memcpy(rec, r, sizeof(r));
+    if (out) {
+        hg_target t = cfg->target;
+        t.sea_alt = r[6];
+        if (cfg->task == HG_TASK_HOVER) {
+            t.north_loc = r[4];
+            t.east_loc = r[5];
+        } else {
+            t.vel = r[7];
+        }
+        *out = t;
+    }
+    return HG_OK;
+}
+
 // Mixed fleets.  A field of an airframe that is not a finite number (its name for the message), or NULL
 static const char* airframe_nonfinite(const hg_airframe& af) {
     constexpr size_t kInt = offsetof(hg_airframe, env_TURB_LVL) / sizeof(double);   // the one integer pair
@@ -3407,6 +3698,9 @@ int32_t hg_set_fleet(hg_env* e, const hg_airframe* classes, const hg_trim_cond* 
     if (e->weather)
         return fail(HG_E_INVALID, "hg_set_fleet: per-env weather is set (hg_set_weather); a fleet together with per-env "
                                   "weather is not supported");
+    if (e->goals)
+        return fail(HG_E_INVALID, "hg_set_fleet: per-env goals are set (hg_set_goals); goals together with a fleet are not "
+                                  "supported");
     if (e->cfg.reset_mode == HG_RESET_RETRIM)
         return fail(HG_E_INVALID, "hg_set_fleet: a fleet needs reset_mode HG_RESET_TEMPLATE (the device re-trim reads one "
                                   "airframe's constants)");
@@ -3659,6 +3953,7 @@ int32_t hg_set_state(hg_env* e, const float* state, const int32_t* counters, voi
                            e->Pf.env_templates ? e->tmpl_env : nullptr, PARAM_ARG(e), (const uint32_t*)state, counters,
                            e->n);
     HIP_TRY(hipGetLastError());
+    if (counters) return goal_redraw(e, (hipStream_t)stream, nullptr, nullptr);   // (box goals follow the episode counters)
     return HG_OK;
 }
 

@@ -888,6 +888,24 @@ HD R reward_hover(const Params<R>& P, const R s[18], const R d[18], bool* succes
     *success = pf > (R)-1 && xf > (R)-1;
     return (m_max(pf, pt) + m_max(xf, xt)) * (R)0.5;
 }
+// ... with the lane's own normalised target in place of P.tgt_n (per-env goals, goals.h): the same expressions
+// in the same order, so the bits are those of a handle whose Params hold that target.  (A copy, not a call from
+// the function above: routing that one through this one moved instructions in kernels that exist already.)
+template <typename R>
+HD R reward_hover(const Params<R>& P, const R tgt_n[3], const R s[18], const R d[18], bool* success) {
+    R pf = 0, pt = 0, xf = 0, xt = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const R pn = s[9 + i] * P.n_t, pdn = d[9 + i] * P.n_t2;
+        const R e = s[15 + i] * P.inv_n_x - tgt_n[i];
+        pf -= pn * pn;
+        pt -= m_sign(pn) * pdn;
+        xf -= e * e;
+        xt -= m_sign(e) * (d[15 + i] * P.inv_n_v);
+    }
+    *success = pf > (R)-1 && xf > (R)-1;
+    return (m_max(pf, pt) + m_max(xf, xt)) * (R)0.5;
+}
 
 // HeliForwardFlight._calculate_reward (helicopter_with_tasks.py:78-115).  QUIRK: divides by the
 // speed, so a helicopter at exactly zero velocity gets a NaN reward like the reference.
@@ -905,6 +923,26 @@ HD R reward_forward(const Params<R>& P, const R s[18], const R d[18], bool* succ
         pt -= m_sign(pn) * pdn;
     }
     const R ev = vn - P.vel_tgt_n, ed = dn - P.dwn_tgt_n;
+    const R vf = -ev * ev, vt = -m_sign(ev) * vdn;
+    const R df = -ed * ed, dtt = -m_sign(ed) * ddn;
+    *success = pf > (R)-1 && vf > (R)-1 && df > (R)-1;
+    return (m_max(pf, pt) + m_max(vf, vt) + m_max(df, dtt)) * (R)(1.0 / 3.0);
+}
+// ... with the lane's own vel_tgt_n and dwn_tgt_n (per-env goals): a copy, as reward_hover's
+template <typename R>
+HD R reward_forward(const Params<R>& P, R vel_tgt_n, R dwn_tgt_n, const R s[18], const R d[18], bool* success) {
+    const R vel = m_sqrt(s[6] * s[6] + s[7] * s[7] + s[8] * s[8]);
+    const R vn = vel * P.inv_n_v;
+    const R vdn = (s[6] * d[6] + s[7] * d[7] + s[8] * d[8]) * m_rcp(vel) * P.inv_n_a;
+    const R dn = s[17] * P.inv_n_x, ddn = d[17] * P.inv_n_v;
+    R pf = 0, pt = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const R pn = s[9 + i] * P.n_t, pdn = d[9 + i] * P.n_t2;
+        pf -= pn * pn;
+        pt -= m_sign(pn) * pdn;
+    }
+    const R ev = vn - vel_tgt_n, ed = dn - dwn_tgt_n;
     const R vf = -ev * ev, vt = -m_sign(ev) * vdn;
     const R df = -ed * ed, dtt = -m_sign(ed) * ddn;
     *success = pf > (R)-1 && vf > (R)-1 && df > (R)-1;

@@ -16,6 +16,7 @@
 #include "retrim.h"
 #include "baked.h"
 #include "weather.h"
+#include "goals.h"
 
 using hg::Params;
 using hg::Template;
@@ -434,6 +435,29 @@ __device__ __forceinline__ uint32_t fleet_wave_tile() {
     else return blockIdx.x * (kStepBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 }
 
+// hg_set_goals' per-env goals (goals.h): a kernel argument of the goal kernels alone, after every other one -- no
+// existing kernel's argument segment moves.  `sample` and `relative` are wave-uniform run-time flags.
+struct GoalArgs {
+    f32x4* rec = nullptr;    // [tiles][2][64] 16-byte words: the normalised goal, the goal in ft and ft/s
+    hgg::Box box = {};       // sample: the box a reset draws the new episode's goal from
+    double n_x = 1.0, n_v = 1.0;   // the normalisers of word 0 (derive()'s, fp64)
+    int32_t sample = 0;      // box mode: a reset draws the goal of episode epi + 1 and stores its record
+    int32_t relative = 0;    // the observation rows minus the goal (word 1)
+};
+// relative observations: the goal's fp32 value off the task's columns (N_POS, E_POS, ALTITUDE; or ALTITUDE and
+// LON_AIR_SPD).  The wind model's carry reads columns 4, 5, 6 and 16, which stay.
+template <int TASK>
+__device__ __forceinline__ void goal_shift(float obs[17], const f32x4& gf) {
+    if (TASK == HG_TASK_HOVER) {
+        obs[13] -= gf.x;
+        obs[14] -= gf.y;
+        obs[15] -= gf.z;
+    } else {
+        obs[15] -= gf.z;
+        obs[1] -= gf.w;
+    }
+}
+
 // What a variant of step_body reads beside StepArgs: a kernel points at the arguments its flags name and
 // leaves the rest at the empty ones, which no code of its variant reads.
 constexpr PolicyArgs kNoPolicy{};
@@ -441,12 +465,14 @@ constexpr AcArgs kNoAc{};
 constexpr BranchArgs kNoBranch{};
 constexpr BranchPolicyArgs kNoBranchPolicy{};
 constexpr WeatherArgs kNoWeather{};
+constexpr GoalArgs kNoGoal{};
 struct StepExtras {
     const PolicyArgs* pol = &kNoPolicy;            // kPolicy
     const AcArgs* ac = &kNoAc;                     // kAc
     const BranchArgs* br = &kNoBranch;             // kBranch
     const BranchPolicyArgs* bp = &kNoBranchPolicy; // kBranch | kPolicy
     const WeatherArgs* wx = &kNoWeather;           // kWeather
+    const GoalArgs* gl = &kNoGoal;                 // kGoal
 };
 
 // step_body's variant: the task, a mask V of the flags below and HELP, the helper kernel's tiles per block
@@ -498,20 +524,31 @@ enum StepFlag : uint32_t {
     // (Params, or kBaked's literals).  The record's two words are requested with the state groups, once
     // per launch; the TEP row inside the wind model's branch for lanes above 1000 ft.
     kWeather = 1u << 9,
+    // (hg_set_goals) the task's target is the lane's own, from gl's per-env record, instead of the handle's
+    // (Params::tgt_n, vel_tgt_n, dwn_tgt_n): word 0 is requested with the state groups, word 1 -- read for
+    // relative observations only -- with them in the lone-wave kernels and the rollouts, after the RK in the
+    // bulk step (its registers are bound to three waves per SIMD).  gl.relative: every observation row is
+    // shifted by the goal of the episode it belongs to.  gl.sample: a reset draws the new episode's goal
+    // (goals.h), stores its record and shifts the reset observation by it; kMulti keeps the goal in
+    // registers across the steps.
+    kGoal = 1u << 10,
 };
 template <int TASK, uint32_t V, int HELP = 0>
 __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n_p, uint64_t seed_p, int64_t envoff_p,
                                           ParamArg Pa, const Template<float>* __restrict__ Tp, const StepArgs& a,
                                           int64_t bid, const StepExtras& x = StepExtras{}) {
     constexpr bool ETA = V & kEta, NT = V & kNT, FEAT = V & kFeat, MULTI = V & kMulti, BAKED = V & kBaked, NTS = V & kNTS,
-                   POLICY = V & kPolicy, AC = V & kAc, BRANCH = V & kBranch, WEATHER = V & kWeather;
+                   POLICY = V & kPolicy, AC = V & kAc, BRANCH = V & kBranch, WEATHER = V & kWeather, GOAL = V & kGoal;
     const PolicyArgs& pol = *x.pol;
     const AcArgs& ac = *x.ac;
     const BranchArgs& br = *x.br;
     const BranchPolicyArgs& bp = *x.bp;
     const WeatherArgs& wx = *x.wx;
+    const GoalArgs& gl = *x.gl;
     static_assert(HELP == 0 || (!ETA && !MULTI), "wind helper waves: in-kernel noise, one step per launch");
     static_assert(!WEATHER || (HELP == 0 && !BRANCH && FEAT), "per-env weather: the one-wave step, per-env templates");
+    static_assert(!GOAL || (FEAT && HELP == 0 && !BRANCH && !WEATHER), "per-env goals: the one-wave step, the optional features");
+    static_assert(!GOAL || TASK == HG_TASK_HOVER || TASK == HG_TASK_FORWARD_FLIGHT, "per-env goals: a task with a target");
     static_assert(!POLICY || (MULTI && HELP == 0), "the in-kernel policy belongs to the rollout");
     static_assert(!AC || POLICY, "log-probabilities and values are the in-kernel policy's");
     static_assert(!BRANCH || (MULTI && FEAT && HELP == 0 && !AC), "branched rollouts: the rollout's steps");
@@ -645,6 +682,15 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
         lw.wm[0] = r0.x; lw.wm[1] = r0.y; lw.wind_dir_cos = r0.z; lw.wind_dir_sin = r0.w;
         lw.sigma_low = r1.x;
         lw.tep_row = wx.tep + (blk0 + tid) * hgw::kTepFloats;
+    }
+    // GOAL: the lane's record, requested behind the state groups (the rows are padded to whole tiles)
+    constexpr bool kGoalEarly = NT || MULTI;   // word 1 with word 0 (else after the RK, when relative)
+    f32x4 gn = {0.f, 0.f, 0.f, 0.f}, gf = {0.f, 0.f, 0.f, 0.f};
+    f32x4* g_rec = nullptr;
+    if constexpr (GOAL) {
+        g_rec = gl.rec + tile * (2 * kTileEnvs);
+        gn = ld_lane(g_rec, lt);
+        if constexpr (kGoalEarly) gf = ld_lane(g_rec + kTileEnvs, lt);
     }
 #ifndef HG_EARLY_PAIRS   // 1: the stages' constant pairs formed while the state loads are in flight (round 5
 #define HG_EARLY_PAIRS 0  // A/B: 7.062 -> 7.088 us, profiles/r05_valu_ab.txt; not adopted)
@@ -830,6 +876,12 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
     const hg::GroundTexels tex_p = hg::ground_fetch(a.hmap, cell_p);
 #endif
     TSTAMP(8, "v"(hs[8]), "v"(hs[11]), "v"(obs[16]));
+    if constexpr (GOAL) {   // relative observations: this row in the frame of the running episode's goal
+        if (gl.relative) {
+            if constexpr (!kGoalEarly) gf = ld_lane(g_rec + kTileEnvs, lt);
+            goal_shift<TASK>(obs, gf);
+        }
+    }
     if (FEAT && !BRANCH && P.reset_retrim && active && !(P.autoreset_next && step < 0)) {   // F8: a reset trims against this wind
         float* wb = a.retrim_wind + blk0;   // [3][N]: three coalesced rows
         st_lane<false>(wb, (uint32_t)tid, W[0]);
@@ -863,8 +915,14 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
     // reward (helicopter_with_tasks.py) and flags (helicopter.py:201-205, 219-240)
     bool success_step = false;
     float rew = 0.f;
-    if (TASK == HG_TASK_HOVER) rew = hg::reward_hover(P, hs, k, &success_step);
-    if (TASK == HG_TASK_FORWARD_FLIGHT) rew = hg::reward_forward(P, hs, k, &success_step);
+    if constexpr (GOAL) {   // the lane's own target
+        const float tgt[3] = {gn.x, gn.y, gn.z};
+        if (TASK == HG_TASK_HOVER) rew = hg::reward_hover(P, tgt, hs, k, &success_step);
+        if (TASK == HG_TASK_FORWARD_FLIGHT) rew = hg::reward_forward(P, gn.w, gn.z, hs, k, &success_step);
+    } else {
+        if (TASK == HG_TASK_HOVER) rew = hg::reward_hover(P, hs, k, &success_step);
+        if (TASK == HG_TASK_FORWARD_FLIGHT) rew = hg::reward_forward(P, hs, k, &success_step);
+    }
 #if HG_EARLY_POST
     const hg::Ground<float> h_post = hg::ground_combine<float>(tex_p, cell_p);
 #else
@@ -1085,6 +1143,24 @@ __device__ __forceinline__ void step_body(float* __restrict__ state_p, int64_t n
             const float v = lane_value(tpl, 22 + c);
             obs[c] = do_reset ? v : obs[c];
         }
+        }
+    }
+    if constexpr (GOAL) {
+        // the new episode's goal, in a wave-uniform branch only waves with a reset take: box mode draws it for
+        // episode epi + 1 (the fp64 divides of its record are here and nowhere else) and stores both words;
+        // the reset observation (the template's, absolute) goes into the new goal's frame
+        if ((gl.sample || gl.relative) && __ballot(do_reset)) {
+            if (do_reset) {
+                if (gl.sample) {
+                    float r[hgg::kRecFloats];
+                    hgg::goal_draw_record(seed_p, (uint64_t)(envoff_p + blk0 + lo), epi + 1, gl.box, gl.n_x, gl.n_v, r);
+                    gn = f32x4{r[0], r[1], r[2], r[3]};
+                    gf = f32x4{r[4], r[5], r[6], r[7]};
+                    st_lane<false>(g_rec, lt, gn);
+                    st_lane<false>(g_rec + kTileEnvs, lt, gf);
+                }
+                if (gl.relative) goal_shift<TASK>(obs, gf);
+            }
         }
     }
     if constexpr (NT) {

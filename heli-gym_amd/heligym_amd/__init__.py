@@ -8,6 +8,7 @@ GPU.  Every step runs in the gfx950 kernels of libheligym_amd.so.
 from ._abi import HeliGymError, load_library  # noqa: F401
 from .config import DT, FPS, make_config  # noqa: F401
 from .envs import Heli, HeliForwardFlight, HeliHover  # noqa: F401
+from .goals import goal_ref, sample_goals  # noqa: F401
 from .evolution import ES, es_grad_ref, es_utilities_ref, pop_fitness_ref  # noqa: F401
 from .planning import MPPI, PolicyMPPI  # noqa: F401
 from .policy import ActorCriticParams, PPOOptState, bc_loss, ppo_loss  # noqa: F401
@@ -17,7 +18,7 @@ from .vector import OBS_NAMES, HeliVecEnv, sample_fleet, sample_weather  # noqa:
 __all__ = ["Heli", "HeliHover", "HeliForwardFlight", "HeliVecEnv", "OBS_NAMES", "register_envs",
            "make_vec", "HeliGymError", "MPPI", "PolicyMPPI", "ActorCriticParams", "PPOOptState", "ppo_loss", "bc_loss",
            "RolloutStats", "rollout_stats_ref", "ES", "es_utilities_ref", "es_grad_ref", "pop_fitness_ref",
-           "sample_weather", "sample_fleet"]
+           "sample_weather", "sample_fleet", "goal_ref", "sample_goals"]
 
 # gymnasium ids of the reference registry (heligym/__init__.py:4-18) -> task
 ENV_IDS = {"Heli-v0": "heli", "HeliHover-v0": "hover", "HeliForwardFlight-v0": "forward_flight"}

@@ -92,6 +92,14 @@ class hg_weather(ctypes.Structure):
     _fields_ = [("turb_level", ctypes.c_float), ("wind_dir_deg", ctypes.c_float), ("wind_spd", ctypes.c_float)]
 
 
+class hg_goal_box(ctypes.Structure):
+    _fields_ = [("lo", hg_target), ("hi", hg_target)]
+
+
+HG_GOAL_OBS_ABSOLUTE, HG_GOAL_OBS_RELATIVE = 0, 1
+HG_GOALS_OFF, HG_GOALS_TABLE, HG_GOALS_BOX = 0, 1, 2
+
+
 class hg_ppo_opt_cfg(ctypes.Structure):
     _fields_ = [("lr", ctypes.c_double), ("lr_dev", ctypes.c_void_p), ("beta1", ctypes.c_double),
                 ("beta2", ctypes.c_double), ("eps", ctypes.c_double), ("max_grad_norm", ctypes.c_float),
@@ -205,6 +213,13 @@ _SIGS = {
     "hg_get_weather": (ctypes.c_int32, [_P, ctypes.POINTER(hg_weather), _P, _P]),
     "hg_weather_constants": (ctypes.c_int32, [ctypes.POINTER(hg_config), ctypes.POINTER(hg_weather),
                                               ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
+    "hg_set_goals": (ctypes.c_int32, [_P, ctypes.POINTER(hg_target), ctypes.POINTER(hg_goal_box), ctypes.c_int32, _P]),
+    "hg_get_goals": (ctypes.c_int32, [_P, ctypes.POINTER(hg_target), ctypes.POINTER(hg_goal_box),
+                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), _P]),
+    "hg_goal_record": (ctypes.c_int32, [ctypes.POINTER(hg_config), ctypes.POINTER(hg_target),
+                                        ctypes.POINTER(ctypes.c_float)]),
+    "hg_goal_draw": (ctypes.c_int32, [ctypes.POINTER(hg_config), ctypes.POINTER(hg_goal_box), ctypes.c_int64,
+                                      ctypes.c_int32, ctypes.POINTER(hg_target), ctypes.POINTER(ctypes.c_float)]),
     "hg_set_fleet": (ctypes.c_int32, [_P, ctypes.POINTER(hg_airframe), ctypes.POINTER(hg_trim_cond), ctypes.c_int32,
                                       ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), _P]),
     "hg_get_fleet": (ctypes.c_int32, [_P, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),

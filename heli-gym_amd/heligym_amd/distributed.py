@@ -5,6 +5,10 @@ Envs never interact, so the data path needs no collective: rank r owns global en
 noise by GLOBAL env id -- results are identical for any number of ranks.  The only optional
 exchange is for a single-host policy: gather every rank's observations (and rewards / flags) to one
 rank, or all-gather them, over RCCL ("nccl" backend = RCCL on ROCm, xGMI between GPUs).
+
+Per-env goals shard the same way: a box goal (`HeliVecEnv.set_goals(box=...)` on `shard.env`) is drawn from
+(seed, GLOBAL env id, episode), so every env meets the same sequence of goals for any number of ranks, and
+`heligym_amd.goal_ref` recomputes it from the global id; a goal table is sliced like any [total, ...] array.
 """
 import torch
 import torch.distributed as dist

@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _abi, config
+from . import goals as _goals
 
 
 class Box:
@@ -412,10 +413,12 @@ class HeliVecEnv(*_VEC_BASES):
         self._check(self.lib.hg_set_max_time(self._h, self.max_time))
 
     def set_target(self, target=None):
-        self._target.update(target or {})
+        new = dict(self._target)
+        new.update(target or {})
         tg = _abi.hg_target()
-        config.fill_target(tg, self._target)
-        self._check(self.lib.hg_set_target(self._h, ctypes.byref(tg)))
+        config.fill_target(tg, new)
+        self._check(self.lib.hg_set_target(self._h, ctypes.byref(tg)))   # (refused while per-env goals are set)
+        self._target = new
 
     def get_target(self):
         return dict(self._target)
@@ -1566,6 +1569,75 @@ class HeliVecEnv(*_VEC_BASES):
         self._check(self.lib.hg_get_weather(self._h, arr, _ptr(tm), self._stream()))
         w = np.frombuffer(arr, dtype=np.float32).reshape(N, 3).copy()
         return {"turb_level": w[:, 0], "wind_dir": w[:, 1], "wind_spd": w[:, 2], "templates": tm}
+
+    def set_goals(self, goals=None, box=None, relative=False):
+        """Per-env goals (hg_set_goals).  `goals`: a dict over the task's fields (hover: north_loc, east_loc,
+        sea_alt; forward_flight: sea_alt, vel), each a scalar or an [N] array; a missing key takes the env's
+        target.  `box`: {field: (lo, hi)} -- every env's goal is redrawn inside it at each reset, in the kernel
+        that resets it, a function of (seed, global env id, episode) that goal_ref restates.  `relative`: the
+        observation rows carry position (or altitude and speed) minus the goal.  With no argument: back to the
+        env's one target.  reset_mode="template" only, not together with set_weather or set_fleet.
+        Synchronises; call it outside graph capture, step inside as before."""
+        N = self.num_envs
+        if goals is None and box is None:
+            if relative:
+                raise ValueError("set_goals: relative observations need goals or a box")
+            self._check(self.lib.hg_set_goals(self._h, None, None, 0, self._stream()))
+            return
+        if goals is not None and box is not None:
+            raise ValueError("set_goals: give goals or a box, not both")
+        fields = _goals.GOAL_FIELDS.get(self.task)
+        if fields is None:
+            raise ValueError(f"set_goals: task {self.task!r} has no target")
+        mode = _abi.HG_GOAL_OBS_RELATIVE if relative else _abi.HG_GOAL_OBS_ABSOLUTE
+        own = dict.fromkeys(config.TARGET_KEYS, 0.0)
+        own.update(self._target)
+        if box is not None:
+            lo, hi = _goals.box_arrays(box, self.task, own)   # (validates keys and ranges)
+            b = _abi.hg_goal_box()
+            config.fill_target(b.lo, own)
+            config.fill_target(b.hi, own)
+            for name in fields:
+                r = box.get(name, own[name])
+                a, c = (r, r) if np.isscalar(r) else r
+                setattr(b.lo, name, float(a))
+                setattr(b.hi, name, float(c))
+            self._check(self.lib.hg_set_goals(self._h, None, ctypes.byref(b), mode, self._stream()))
+            return
+        if not isinstance(goals, dict):
+            raise ValueError(f"set_goals: goals must be a dict over {fields}")
+        unknown = sorted(set(goals) - set(fields))
+        if unknown:
+            raise ValueError(f"set_goals: unknown field(s) {unknown} for task {self.task!r}; its fields are {fields}")
+        arr = (_abi.hg_target * N)()
+        rows = np.frombuffer(arr, dtype=np.float64).reshape(N, len(config.TARGET_KEYS))
+        for j, name in enumerate(config.TARGET_KEYS):
+            v = goals.get(name, own[name]) if name in fields else own[name]
+            a = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float64)
+            if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != N):
+                raise ValueError(f"set_goals: {name} must be a scalar or have {N} entries, got shape {a.shape}")
+            if name in fields and not np.all(np.isfinite(a)):
+                raise ValueError(f"set_goals: {name} has a non-finite value")
+            rows[:, j] = a
+        self._check(self.lib.hg_set_goals(self._h, arr, None, mode, self._stream()))
+
+    def get_goals(self):
+        """dict of [N] float64 arrays over the task's fields (the env's one target while no goals are set; in box
+        mode the float32 values the device table holds now), plus `mode` ("off", "table" or "box"), `box`
+        ({field: (lo, hi)} or None) and `relative`."""
+        N = self.num_envs
+        arr = (_abi.hg_target * N)()
+        b = _abi.hg_goal_box()
+        mode, om = ctypes.c_int32(), ctypes.c_int32()
+        self._check(self.lib.hg_get_goals(self._h, arr, ctypes.byref(b), ctypes.byref(mode), ctypes.byref(om), self._stream()))
+        rows = np.frombuffer(arr, dtype=np.float64).reshape(N, len(config.TARGET_KEYS))
+        fields = _goals.GOAL_FIELDS.get(self.task, ())
+        out = {name: rows[:, config.TARGET_KEYS.index(name)].copy() for name in fields}
+        out["mode"] = ("off", "table", "box")[mode.value]
+        out["box"] = ({name: (getattr(b.lo, name), getattr(b.hi, name)) for name in fields}
+                      if mode.value == _abi.HG_GOALS_BOX else None)
+        out["relative"] = om.value == _abi.HG_GOAL_OBS_RELATIVE
+        return out
 
     def set_fleet(self, airframes, tile_class=None, envs_per_class=None, conds=None):
         """Mixed fleet (hg_set_fleet): one airframe class per 64-env state tile.  `airframes` is a list of

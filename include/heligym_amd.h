@@ -860,6 +860,59 @@ int32_t hg_get_weather(hg_env* env, hg_weather* out_host, float* templates_dev, 
  * validated for NULL only (no constant of a weather depends on the rest of the configuration today). */
 int32_t hg_weather_constants(const hg_config* cfg, const hg_weather* w, float record[8], float tep_row[16]);
 
+/* ---- Per-env goals: task targets that differ across one handle's envs, optionally redrawn at every reset.
+ *
+ * hg_config::target (hg_set_target) is one target for the whole handle.  A goal table gives each env its own;
+ * an env given a goal steps bitwise like an env of a handle whose target is that goal (same seed, global env
+ * id and reset template).  HG_TASK_HOVER uses north_loc, east_loc and sea_alt; HG_TASK_FORWARD_FLIGHT uses
+ * sea_alt and vel; the other fields of a goal are not looked at.  HG_TASK_HELI has no target: HG_E_INVALID.
+ *
+ * Two modes.  TABLE: `goals_host` [N], kept until changed.  BOX: a closed range per field; env i's goal in
+ * episode e is hg_goal_draw(cfg, box, env_offset + i, e) -- a pure function of the handle's seed, the env's
+ * global id, the episode counter (the one the turbulence noise is keyed by) and the box, so it does not depend
+ * on the batch or on how the envs are sharded.  The kernel that resets an env draws the new episode's goal and
+ * stores it into the table (no host work: the stepping calls stay capturable); hg_reset and hg_set_state with
+ * counters redraw it, so the table always holds draw(seed, gid_i, episode_i).
+ *
+ * obs_mode HG_GOAL_OBS_RELATIVE: every observation row the stepping calls produce has the goal's fp32 value
+ * subtracted, in fp32, from columns 13, 14, 15 (N_POS, E_POS, ALTITUDE; hover) or from column 15 and column 1
+ * (LON_AIR_SPD minus the target speed; forward flight) -- obs, final_obs, final_obs_rows, the in-kernel policy's
+ * input and the terminal forward pass of next_value, each in the frame of the goal of the episode the row
+ * belongs to (a terminal observation the ending episode's, the reset observation the new one's), and the
+ * rows hg_reset writes.  Rewards, flags and the state are those of absolute observations.
+ *
+ * Both NULL: back to the handle-wide target.  Synchronises with the device; not capturable.
+ * HG_E_INVALID with a message that names the cause: both goals_host and box given; a non-finite value; lo > hi;
+ * vel <= 0 for forward flight; an obs_mode outside the enum; HG_TASK_HELI; reset_mode HG_RESET_RETRIM (the trim
+ * kernel writes the observation rows); a handle with per-env weather or a fleet (hg_set_weather and
+ * hg_set_fleet refuse a goal handle too).  While goals are set: hg_set_target returns HG_E_INVALID ("pass goals
+ * to hg_set_goals"), and so do hg_rollout_pop, hg_rollout_branch and hg_rollout_branch_policy.  hg_step,
+ * hg_step_rows, hg_step_chained, hg_rollout, hg_rollout_policy and hg_rollout_ac honour the goals at every N
+ * through kernels of their own (the lone-wave and the bulk step with the optional features; no helper-wave,
+ * non-temporal bulk or run-time specialised variant), counted by hg_debug_launches in the lone-wave or bulk
+ * bucket.  hg_set_max_time, hg_reset, hg_get_state, hg_set_state and per-env reset templates work as before. */
+typedef struct hg_goal_box {
+    hg_target lo, hi;
+} hg_goal_box;
+enum { HG_GOAL_OBS_ABSOLUTE = 0, HG_GOAL_OBS_RELATIVE = 1 };
+enum { HG_GOALS_OFF = 0, HG_GOALS_TABLE = 1, HG_GOALS_BOX = 2 };
+int32_t hg_set_goals(hg_env* env, const hg_target* goals_host /* [N] or NULL */, const hg_goal_box* box /* or NULL */,
+                     int32_t obs_mode, void* stream);
+/* Any output may be NULL.  goals_host [N]: each env's goal now (the handle-wide target while none is set; in box
+ * mode the fp32 values the table holds; heading is the handle's).  box: the box (zeros unless mode is BOX).
+ * Synchronises with `stream`. */
+int32_t hg_get_goals(hg_env* env, hg_target* goals_host, hg_goal_box* box, int32_t* mode, int32_t* obs_mode,
+                     void* stream);
+/* Host only: the record hg_set_goals uploads for a target, rec = {north / n_x, east / n_x, -sea_alt / n_x,
+ * vel / n_v, north, east, sea_alt, vel}: rec[0..2] bitwise the tgt_n, rec[3] the vel_tgt_n and rec[2] the
+ * dwn_tgt_n of a handle configured with that target (hg_debug_params). */
+int32_t hg_goal_record(const hg_config* cfg, const hg_target* target, float rec[8]);
+/* Host only: the device's draw for global env id `global_env` in episode `episode` of a handle configured as
+ * `cfg` (its seed, task, airframe and target, which fills the fields the task does not use).  out (or NULL):
+ * the goal; rec (or NULL): its record. */
+int32_t hg_goal_draw(const hg_config* cfg, const hg_goal_box* box, int64_t global_env, int32_t episode,
+                     hg_target* out, float rec[8]);
+
 /* ---- Mixed fleets: airframes that differ across one handle's envs, one airframe class per 64-env state tile.
  *
  * A handle steps every env with one airframe's constants.  A fleet gives each state tile (envs 64 t .. 64 t + 63,
