@@ -818,6 +818,37 @@ __global__ __launch_bounds__(kBlock) void eta_kernel(const float* state, int64_t
     out[3 * i + 2] = eta[2];
 }
 
+// hg_debug_task: the task layer alone (the reward functions the step kernels call, physics.h) on given rows of
+// post-step state and k4 derivatives, with the handle's constants; with per-env goals, row i under the record
+// of env i % n_envs through the goal forms, as the goal kernels call them.
+__global__ __launch_bounds__(kBlock) void task_kernel(const float* heli, const float* dots, int64_t n, int32_t task,
+                                                      const Params<float>* Pp, const float* goal_rec, int64_t n_envs,
+                                                      float* reward, uint8_t* success) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const Params<float>& P = *Pp;
+    float s[18], d[18];
+#pragma unroll
+    for (int k = 0; k < 18; ++k) {
+        s[k] = heli[18 * i + k];
+        d[k] = dots[18 * i + k];
+    }
+    bool ok = false;
+    float r = 0.f;
+    if (goal_rec) {
+        const int64_t j = i % n_envs;   // word 0 of env j (goals.h rec_index)
+        const float* g = goal_rec + (j / hgg::kTile) * hgg::kTile * hgg::kRecFloats + (j % hgg::kTile) * 4;
+        const float tgt[3] = {g[0], g[1], g[2]};
+        if (task == HG_TASK_HOVER) r = hg::reward_hover(P, tgt, s, d, &ok);
+        if (task == HG_TASK_FORWARD_FLIGHT) r = hg::reward_forward(P, g[3], g[2], s, d, &ok);
+    } else {
+        if (task == HG_TASK_HOVER) r = hg::reward_hover(P, s, d, &ok);
+        if (task == HG_TASK_FORWARD_FLIGHT) r = hg::reward_forward(P, s, d, &ok);
+    }
+    reward[i] = r;
+    success[i] = ok ? 1 : 0;
+}
+
 // hg_set_policy: the caller's weights into the handle's packed image, each matrix element where the
 // lane that uses it as a matrix operand loads it from (layout: policy_mlp.h).  The value head's
 // elements are not written (value_pack_kernel's), so a head set before or after stays.
@@ -3633,6 +3664,32 @@ int32_t hg_goal_record(const hg_config* cfg, const hg_target* target, float rec[
     return HG_OK;
 }
 
+int32_t hg_debug_task_host(const hg_config* cfg, const double* heli, const double* dots, const hg_target* goals, int64_t n,
+                           double* reward, uint8_t* success) {
+    if (!cfg || n < 0 || (n > 0 && (!heli || !dots || !reward || !success)))
+        return fail(HG_E_INVALID, "hg_debug_task_host: bad arguments");
+    if (cfg->task != HG_TASK_HOVER && cfg->task != HG_TASK_FORWARD_FLIGHT)
+        return fail(HG_E_INVALID, "hg_debug_task_host: HG_TASK_HELI has no reward");
+    const Params<double> P = derive<double>(*cfg, 2, 2);   // (the task layer reads no terrain constant)
+    for (int64_t i = 0; i < n; ++i) {
+        const double *s = heli + 18 * i, *d = dots + 18 * i;
+        bool ok = false;
+        double r;
+        if (goals) {   // the goal kernels' view: the fp32 record of the env's target
+            float rec[hgg::kRecFloats];
+            goal_record_of(*cfg, goals[i], rec);
+            const double tgt[3] = {(double)rec[0], (double)rec[1], (double)rec[2]};
+            r = cfg->task == HG_TASK_HOVER ? hg::reward_hover<double>(P, tgt, s, d, &ok)
+                                           : hg::reward_forward<double>(P, (double)rec[3], (double)rec[2], s, d, &ok);
+        } else {
+            r = cfg->task == HG_TASK_HOVER ? hg::reward_hover<double>(P, s, d, &ok) : hg::reward_forward<double>(P, s, d, &ok);
+        }
+        reward[i] = r;
+        success[i] = ok ? 1 : 0;
+    }
+    return HG_OK;
+}
+
 int32_t hg_goal_draw(const hg_config* cfg, const hg_goal_box* box, int64_t global_env, int32_t episode, hg_target* out,
                      float rec[8]) {
     if (!cfg || !box) return fail(HG_E_INVALID, "hg_goal_draw: NULL argument");
@@ -3981,6 +4038,21 @@ int32_t hg_debug_eta(hg_env* e, float* eta, void* stream) {
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     hipLaunchKernelGGL(eta_kernel, dim3(grid_for(e->n)), dim3(kBlock), 0, (hipStream_t)stream, e->state, e->n,
                        (uint64_t)e->cfg.seed, (int64_t)e->cfg.env_offset, PARAM_ARG(e), eta);
+    HIP_TRY(hipGetLastError());
+    return HG_OK;
+}
+
+int32_t hg_debug_task(hg_env* e, const float* heli, const float* dots, float* reward, uint8_t* success, int64_t n,
+                      void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (n < 0 || (n > 0 && (!heli || !dots || !reward || !success))) return fail(HG_E_INVALID, "hg_debug_task: bad arguments");
+    if (e->cfg.task != HG_TASK_HOVER && e->cfg.task != HG_TASK_FORWARD_FLIGHT)
+        return fail(HG_E_INVALID, "hg_debug_task: HG_TASK_HELI has no reward");
+    if (n == 0) return HG_OK;
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    hipLaunchKernelGGL(task_kernel, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, heli, dots, n, e->cfg.task,
+                       PARAM_ARG(e), e->goals ? e->goal_rec : nullptr, e->n, reward, success);
     HIP_TRY(hipGetLastError());
     return HG_OK;
 }

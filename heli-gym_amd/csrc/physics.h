@@ -189,7 +189,13 @@ HD bool wave_any(bool c) {
 // subtract-with-borrow and int -> float convert on the reward's dependent chain: compare, bit select, select
 HD float m_sign(float x) { return (x < 0.f || x > 0.f) ? __builtin_copysignf(1.f, x) : 0.f; }
 HD double m_sign(double x) { return (x < 0.0 || x > 0.0) ? __builtin_copysign(1.0, x) : 0.0; }
-template <typename R> HD R m_max(R a, R b) { return a > b ? a : b; }
+// Python's max(a, b): b only where b > a holds, so a NaN b leaves a and a NaN a stays (the rewards pass their
+// final term first, helicopter_with_tasks.py:37-39).  One compare and one select, as a > b ? a : b was.
+template <typename R> HD R m_max(R a, R b) { return b > a ? b : a; }
+// a floor: max(a, lo) with lo a constant that is no NaN.  The values are m_max's for every a that is no NaN; a NaN
+// a gives lo (the reference's max(a, lo) keeps the NaN of a state that has diverged already).  Kept apart
+// because this form is one v_max_f32 and the other a compare and a select, in every step kernel's four stages.
+template <typename R> HD R m_floor_at(R a, R lo) { return a > lo ? a : lo; }
 
 constexpr double kPi = 3.14159265358979323846;
 constexpr double kEps = 1e-4;                  // helicopter_dynamics.py:15, wind_dynamics.py:10
@@ -461,7 +467,7 @@ HD WindPar<R> wind_params(const Params<R>& P, const WK& K, const R carry[4]) {
     const R h = carry[3];
     R Lu, Lv, Lw, s_u, s_v, s_w, ca, sa;
     auto low_alt = [&]() {                    // low altitude
-        const R hl = m_max(h, (R)10);
+        const R hl = m_floor_at(h, (R)10);
         const R lb = m_log2((R)0.177 + (R)0.000823 * hl);
         Lu = hl * m_exp2((R)-1.2 * lb);
         Lv = (R)0.5 * Lu;
@@ -757,7 +763,7 @@ HD Loads<R> tail_loads(const Params<R>& P, const R* __restrict__ s, const Contro
     const R power_tr = thr_t * (vi_tr - vr);
     const R rh = (R)0.5 * rho;
     // ---- horizontal tail
-    const R v_dw = m_max(vi_mr - wa, (R)kEps);
+    const R v_dw = m_floor_at(vi_mr - wa, (R)kEps);
     const R d_dw = ua * m_rcp(v_dw) * P.ht_dw_k - P.ht_dw_c;
     const R eps_ht = (d_dw > (R)0 && d_dw < P.mr_R) ? (R)2 * ((R)1 - d_dw * P.mr_inv_R) : (R)0;
     const R wa_ht = wa - eps_ht * vi_mr + P.ht_D * q;
@@ -908,7 +914,8 @@ HD R reward_hover(const Params<R>& P, const R tgt_n[3], const R s[18], const R d
 }
 
 // HeliForwardFlight._calculate_reward (helicopter_with_tasks.py:78-115).  QUIRK: divides by the
-// speed, so a helicopter at exactly zero velocity gets a NaN reward like the reference.
+// speed, so at exactly zero velocity the terminal speed term is NaN (0 * rcp(0)); the reference's
+// max(final, terminal) then keeps the final term and the reward is finite, and so does m_max.
 template <typename R>
 HD R reward_forward(const Params<R>& P, const R s[18], const R d[18], bool* success) {
     const R vel = m_sqrt(s[6] * s[6] + s[7] * s[7] + s[8] * s[8]);

@@ -718,7 +718,7 @@ HD void stage_f32(const Params<float>& P, const StepK& K, const StepCtx& c, cons
     const float p_extra = power_fus - P.wt * n2;                 // + climb power (:435, :446-447)
 
     // ---- horizontal (:322-345) and vertical (:347-361) tail, packed as (HT, VT)
-    const float v_dw = m_max(-wa_f0, (float)kEps);
+    const float v_dw = m_floor_at(-wa_f0, (float)kEps);
     const float d_dw = ua * m_rcp(v_dw) * P.ht_dw_k - P.ht_dw_c;
     const float eps_ht = (d_dw > 0.f && d_dw < P.mr_R) ? 2.f + d_dw * P.f_m2_R : 0.f;
     const float wa_ht = wa - eps_ht * s.vi.x + P.ht_D * q;

@@ -206,6 +206,9 @@ _SIGS = {
     "hg_clock_stamp": (ctypes.c_int32, [_P, _P]),
     "hg_debug_eta": (ctypes.c_int32, [_P, _P, _P]),
     "hg_debug_philox": (ctypes.c_int32, [_P, _P, ctypes.c_int64, _P]),
+    "hg_debug_task": (ctypes.c_int32, [_P, _P, _P, _P, _P, ctypes.c_int64, _P]),
+    "hg_debug_task_host": (ctypes.c_int32, [ctypes.POINTER(hg_config), _P, _P, ctypes.POINTER(hg_target), ctypes.c_int64,
+                                            _P, _P]),
     "hg_trim_conds_batch": (ctypes.c_int32, [_P, ctypes.POINTER(hg_trim_cond), ctypes.c_int64, _P, _P, _P, _P,
                                              _P, _P]),
     "hg_set_reset_templates": (ctypes.c_int32, [_P, _P, _P]),

@@ -1733,10 +1733,54 @@ class HeliVecEnv(*_VEC_BASES):
         self._check(self.lib.hg_debug_eta(self._h, _ptr(out), self._stream()))
         return out
 
+    def debug_task(self, heli, dots, out=None):
+        """Diagnostic: the task layer alone (hg_debug_task) on rows of post-step heli state [n,18] and k4
+        derivatives [n,18], float32 on the env's device: (reward [n] float32, success_step [n] uint8) under the
+        env's target, or, while per-env goals are set, row i under the goal of env i % num_envs."""
+        t = self.torch
+        n = int(heli.shape[0])
+        for name, x in (("heli", heli), ("dots", dots)):
+            if (tuple(x.shape) != (n, 18) or x.dtype != t.float32 or x.device != t.device(self.device)
+                    or not x.is_contiguous()):
+                raise ValueError(f"debug_task: {name} must be a contiguous float32 ({n}, 18) tensor on {self.device}")
+        if out is None:
+            out = (t.empty((n,), dtype=t.float32, device=self.device), t.empty((n,), dtype=t.uint8, device=self.device))
+        rew, succ = out
+        if (tuple(rew.shape) != (n,) or rew.dtype != t.float32 or tuple(succ.shape) != (n,) or succ.dtype != t.uint8
+                or rew.device != t.device(self.device) or succ.device != t.device(self.device)
+                or not rew.is_contiguous() or not succ.is_contiguous()):
+            raise ValueError(f"debug_task: out must be (float32 ({n},), uint8 ({n},)) contiguous tensors on {self.device}")
+        self._check(self.lib.hg_debug_task(self._h, _ptr(heli), _ptr(dots), _ptr(rew), _ptr(succ), n, self._stream()))
+        return out
+
     def random_actions(self, out, seed, step, lo=-1.0, hi=1.0):
         self._check(self.lib.hg_random_actions(self._h, _ptr(out), int(seed), int(step), float(lo),
                                                float(hi), self._stream()))
         return out
+
+
+def task_reward_host(cfg, heli, dots, goals=None):
+    """Diagnostic, no device: the task layer in fp64 on the host (hg_debug_task_host) for rows of post-step heli
+    state [n,18] and k4 derivatives [n,18] under `cfg` (config.make_config): (reward [n] float64, success_step [n]
+    bool).  goals: None (cfg's own target), or a dict over target fields (scalars or [n] arrays, a missing field
+    is cfg's) -- row i then goes through the per-env goal forms with the fp32 record of its goal."""
+    lib = _abi.load_library()
+    h = np.ascontiguousarray(heli, dtype=np.float64)
+    d = np.ascontiguousarray(dots, dtype=np.float64)
+    if h.ndim != 2 or h.shape[1] != 18 or d.shape != h.shape:
+        raise ValueError("task_reward_host: heli and dots must be [n, 18]")
+    n = h.shape[0]
+    arr = None
+    if goals is not None:
+        arr = (_abi.hg_target * max(n, 1))()
+        rows = np.frombuffer(arr, dtype=np.float64).reshape(max(n, 1), len(config.TARGET_KEYS))
+        for j, name in enumerate(config.TARGET_KEYS):
+            rows[:, j] = np.asarray(goals.get(name, getattr(cfg.target, name)), dtype=np.float64)
+    rew = np.empty(n, dtype=np.float64)
+    succ = np.empty(n, dtype=np.uint8)
+    _abi.check(lib.hg_debug_task_host(ctypes.byref(cfg), h.ctypes.data, d.ctypes.data, arr, n, rew.ctypes.data,
+                                      succ.ctypes.data), lib)
+    return rew, succ.astype(bool)
 
 
 def _airframe_fields(af):

@@ -912,6 +912,13 @@ int32_t hg_goal_record(const hg_config* cfg, const hg_target* target, float rec[
  * the goal; rec (or NULL): its record. */
 int32_t hg_goal_draw(const hg_config* cfg, const hg_goal_box* box, int64_t global_env, int32_t episode,
                      hg_target* out, float rec[8]);
+/* Diagnostic, host only, fp64: the task layer (reward and success_step of cfg's task, the functions the step
+ * kernels instantiate in fp32) on n rows of post-step heli state [n,18] and k4 derivatives [n,18].  goals NULL:
+ * under cfg's own target (the constants of a handle configured as cfg).  goals [n]: row i under goals[i] through
+ * the per-env goal forms, fed the fp32 record hg_goal_record gives for it, as the goal kernels are.
+ * reward [n], success [n] (0 / 1).  HG_TASK_HELI is refused. */
+int32_t hg_debug_task_host(const hg_config* cfg, const double* heli, const double* dots, const hg_target* goals,
+                           int64_t n, double* reward, uint8_t* success);
 
 /* ---- Mixed fleets: airframes that differ across one handle's envs, one airframe class per 64-env state tile.
  *
@@ -1033,6 +1040,14 @@ int32_t hg_random_actions(hg_env* env, float* actions_dev, uint64_t seed, uint64
  * episode index) and Box-Muller, computed by the same device function from the env's current
  * counters.  A step given these values as eta_dev is bitwise the in-kernel step. */
 int32_t hg_debug_eta(hg_env* env, float* eta_dev, void* stream);
+
+/* Diagnostic (parity tests): the task layer alone, fp32, on n rows of post-step heli state heli_dev [n,18] and k4
+ * derivatives dots_dev [n,18]: the reward functions the step kernels call, with the handle's device constants
+ * (its target, after hg_set_target).  While per-env goals are set, row i is evaluated under the record of env
+ * i % N through the goal forms.  reward_dev [n] fp32, success_dev [n] u8 (success_step).  n is any count >= 0;
+ * it changes no state of the handle.  HG_TASK_HELI is refused. */
+int32_t hg_debug_task(hg_env* env, const float* heli_dev, const float* dots_dev, float* reward_dev,
+                      uint8_t* success_dev, int64_t n, void* stream);
 
 /* Diagnostic (known-answer tests): the device Philox4x32-10 on `count` rows of in_dev
  * {ctr0, ctr1, ctr2, ctr3, key0, key1} (u32) -> out_dev [count,4] u32.  It has no handle: it runs on

@@ -662,10 +662,11 @@ void or_heli_step(const or_model* m, double s[18], const double act[4], const do
 /* ------------------------------------------------------------------ tasks and flags */
 
 static double sgn(double x) { return (x > 0) - (x < 0); }
+/* Python's max(final, terminal) (helicopter_with_tasks.py:37-39): a NaN terminal term leaves the final one */
+static double pymax(double a, double b) { return b > a ? b : a; }
 
 /* HeliHover._calculate_reward (helicopter_with_tasks.py:27-52) */
-static double reward_hover(const or_model* m, const double s[18], const double d[18], int* success) {
-    const hg_target* t = &m->cfg.target;
+static double reward_hover(const or_model* m, const hg_target* t, const double s[18], const double d[18], int* success) {
     double tgt[3] = {F32(t->north_loc) / m->n_x, F32(t->east_loc) / m->n_x, F32(-t->sea_alt) / m->n_x};
     tgt[0] = F32(tgt[0]); tgt[1] = F32(tgt[1]); tgt[2] = F32(tgt[2]);
     double pf = 0, pt = 0, xf = 0, xt = 0;
@@ -678,12 +679,11 @@ static double reward_hover(const or_model* m, const double s[18], const double d
         xt -= sgn(xn - tgt[i]) * xdn;
     }
     *success = pf > -1.0 && xf > -1.0;
-    return ((pf > pt ? pf : pt) + (xf > xt ? xf : xt)) / 2.0;
+    return (pymax(pf, pt) + pymax(xf, xt)) / 2.0;
 }
 
 /* HeliForwardFlight._calculate_reward (helicopter_with_tasks.py:78-115) */
-static double reward_ff(const or_model* m, const double s[18], const double d[18], int* success) {
-    const hg_target* t = &m->cfg.target;
+static double reward_ff(const or_model* m, const hg_target* t, const double s[18], const double d[18], int* success) {
     double vel = sqrt(s[6] * s[6] + s[7] * s[7] + s[8] * s[8]);
     double vn = vel / m->n_v;
     double vdn = (s[6] * d[6] + s[7] * d[7] + s[8] * d[8]) / vel / m->n_a;
@@ -699,8 +699,21 @@ static double reward_ff(const or_model* m, const double s[18], const double d[18
     double vf = -(vn - vt) * (vn - vt), vtr = -sgn(vn - vt) * vdn;
     double df = -(dn - dt_) * (dn - dt_), dtr = -sgn(dn - dt_) * ddn;
     *success = pf > -1.0 && vf > -1.0 && df > -1.0;
-    double pr = pf > pt ? pf : pt, vr = vf > vtr ? vf : vtr, dr = df > dtr ? df : dtr;
-    return (pr + vr + dr) / 3.0;
+    return (pymax(pf, pt) + pymax(vf, vtr) + pymax(df, dtr)) / 3.0;
+}
+
+/* The task layer alone: reward and success_step of `task` under `target` for n rows of post-step state and
+ * k4 derivatives. */
+int or_task_reward(const or_model* m, int task, const hg_target* target, const double* heli, const double* dots,
+                   int64_t n, double* reward, int32_t* success) {
+    if (task != HG_TASK_HOVER && task != HG_TASK_FORWARD_FLIGHT) return -1;
+    for (int64_t i = 0; i < n; i++) {
+        int ok;
+        reward[i] = task == HG_TASK_HOVER ? reward_hover(m, target, heli + 18 * i, dots + 18 * i, &ok)
+                                          : reward_ff(m, target, heli + 18 * i, dots + 18 * i, &ok);
+        success[i] = ok;
+    }
+    return 0;
 }
 
 /* Heli._is_failed (helicopter.py:226-234), post-step state and k4 dots. */
@@ -727,8 +740,8 @@ void or_step(const or_model* m, or_env* e, const double act[4], const double eta
     e->state_f32 = 0;
     memcpy(o->obs, e->obs, sizeof(o->obs));
     int sh, sf;
-    o->reward_hover = reward_hover(m, e->heli, e->dots, &sh);
-    o->reward_ff = reward_ff(m, e->heli, e->dots, &sf);
+    o->reward_hover = reward_hover(m, &m->cfg.target, e->heli, e->dots, &sh);
+    o->reward_ff = reward_ff(m, &m->cfg.target, e->heli, e->dots, &sf);
     o->success_hover = sh;
     o->success_ff = sf;
     int task = m->cfg.task, succ;

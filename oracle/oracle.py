@@ -78,6 +78,9 @@ class Oracle:
         lib.or_rollout.argtypes = [ctypes.c_void_p, ctypes.POINTER(_abi.hg_trim_result), ctypes.c_int64,
                                    ctypes.c_int64, ctypes.c_uint64, PD]
         lib.or_set_stage_f32.argtypes = [ctypes.c_int]
+        lib.or_task_reward.restype = ctypes.c_int
+        lib.or_task_reward.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(_abi.hg_target), PD, PD,
+                                       ctypes.c_int64, PD, ctypes.POINTER(ctypes.c_int32)]
         self.cfg = cfg
         self._hmap = np.ascontiguousarray(hmap_u16, dtype=np.uint16)
         self.m = lib.or_create(ctypes.byref(cfg), self._hmap.ctypes.data, self._hmap.shape[0],
@@ -153,6 +156,22 @@ class Oracle:
         self.lib.or_step(self.m, ctypes.byref(e), _dp(a), _dp(n), ctypes.byref(o))
         self.last_lg_margin = self.lib.or_diag_lg_margin()
         return o
+
+    def task_reward(self, task, target, heli, dots):
+        """The task layer alone (or_task_reward): (reward [n], success_step [n] bool) of `task` ("hover" or
+        "forward_flight") under the target dict for rows of post-step state [n,18] and k4 derivatives [n,18]."""
+        from heligym_amd import config
+        tg = self._abi.hg_target()
+        config.fill_target(tg, target)
+        h = np.ascontiguousarray(heli, dtype=np.float64).reshape(-1, 18)
+        d = np.ascontiguousarray(dots, dtype=np.float64).reshape(-1, 18)
+        rew = np.zeros(len(h))
+        succ = np.zeros(len(h), dtype=np.int32)
+        rc = self.lib.or_task_reward(self.m, config.TASKS[task], ctypes.byref(tg), _dp(h), _dp(d), len(h), _dp(rew),
+                                     succ.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        if rc != 0:
+            raise ValueError(f"oracle: task {task!r} has no reward")
+        return rew, succ.astype(bool)
 
     def set_stage_f32(self, on):
         """Diagnostic: RK stage inputs and the updated state rounded to float32 (an fp32

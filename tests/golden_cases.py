@@ -113,41 +113,81 @@ def _terminal_bounds(arg, arg_tol, d):
     return fixed.sum(axis=-1) - span.sum(axis=-1), fixed.sum(axis=-1) + span.sum(axis=-1)
 
 
+REWARD_ABS, REWARD_REL = 2e-4, 2e-5   # the reward contract: |dr| <= REWARD_ABS + REWARD_REL * (sum of |term|)
+TRAJ_ABS, TRAJ_REL = 1e-3, 1e-4       # contract (ii), free-running trajectories
+
+
+def _traj_tol(x):
+    return TRAJ_ABS + TRAJ_REL * np.abs(x)
+
+
+def _pymax(final, terminal):
+    """Python's max(final, terminal) (helicopter_with_tasks.py:37,44): the terminal term only where
+    `terminal > final` holds, so a NaN terminal term leaves the final one and a NaN final one stays."""
+    return np.where(terminal > final, terminal, final)
+
+
+def _mag(a):
+    """|a| where finite, else 0: a term that is inf or NaN drops out of the reward's rounding scale."""
+    return np.where(np.isfinite(a), np.abs(a), 0.0)
+
+
+def task_terms(heli, dots, task, n_t=np.sqrt(2 * 18 / 32.2), n_x=36.0, n_v=np.sqrt(2 * 18 * 32.2), n_a=32.2,
+               north_loc=0.0, east_loc=0.0, sea_alt=4000.0, vel=100.0, tol=None):
+    """The task layer's terms (helicopter_with_tasks.py:27-52, 78-115) in fp64 for rows of post-step
+    state and k4 derivatives; the target fields are scalars or one value per row.  Returns a dict:
+    args [n, A] every sign() argument, arg_tol [n, A] its ambiguity tolerance (the state tolerance
+    `tol` carried to the argument), terms [n, A] what each sign multiplies, final [n, G] the
+    *_final_reward of every group, groups: the columns of args of each group."""
+    _tol = tol or globals()["_tol"]
+    h = np.asarray(heli, dtype=np.float64)
+    d = np.asarray(dots, dtype=np.float64)
+    n = len(h)
+    bc = lambda v: np.broadcast_to(np.asarray(v, dtype=np.float64), (n,))  # noqa: E731
+    with np.errstate(all="ignore"):
+        pn, pdn = h[:, 9:12] * n_t, d[:, 9:12] * n_t ** 2
+        pf = -(pn ** 2).sum(axis=1)
+        ptol = _tol(h[:, 9:12]) * n_t
+        if task == "hover":
+            # np.array([...], float32) / 36 stays float32 (:33)
+            tgt = (np.stack([bc(north_loc), bc(east_loc), -bc(sea_alt)], axis=1).astype(np.float32)
+                   / np.float32(n_x)).astype(np.float64)
+            e = h[:, 15:18] / n_x - tgt
+            return {"args": np.concatenate([pn, e], axis=1),
+                    "arg_tol": np.concatenate([ptol, _tol(h[:, 15:18]) / n_x], axis=1),
+                    "terms": np.concatenate([pdn, d[:, 15:18] / n_v], axis=1),
+                    "final": np.stack([pf, -(e ** 2).sum(axis=1)], axis=1), "groups": ((0, 1, 2), (3, 4, 5))}
+        v = np.sqrt((h[:, 6:9] ** 2).sum(axis=1))
+        # np.array(vel, float32) / np.float64 is float64; np.array(-alt, float32) / 36 stays float32 (:87-88)
+        ev = v / n_v - bc(vel).astype(np.float32).astype(np.float64) / n_v
+        vdn = (h[:, 6:9] * d[:, 6:9]).sum(axis=1) / v / n_a
+        ed = h[:, 17] / n_x - ((-bc(sea_alt)).astype(np.float32) / np.float32(n_x)).astype(np.float64)
+        return {"args": np.concatenate([pn, ev[:, None], ed[:, None]], axis=1),
+                "arg_tol": np.concatenate([ptol, (_tol(v) / n_v)[:, None], (_tol(h[:, 17]) / n_x)[:, None]], axis=1),
+                "terms": np.concatenate([pdn, vdn[:, None], (d[:, 17] / n_v)[:, None]], axis=1),
+                "final": np.stack([pf, -ev ** 2, -ed ** 2], axis=1), "groups": ((0, 1, 2), (3,), (4,))}
+
+
 def reward_bounds(heli, dots, task, n_t=np.sqrt(2 * 18 / 32.2), n_x=36.0, n_v=np.sqrt(2 * 18 * 32.2),
-                  n_a=32.2, sea_alt=4000.0, vel=100.0, tol=None):
+                  n_a=32.2, sea_alt=4000.0, vel=100.0, tol=None, north_loc=0.0, east_loc=0.0):
     """Interval of task rewards (helicopter_with_tasks.py:27-52, 78-115) consistent with the
     post-step state `heli` and k4 derivatives `dots` once every sign() argument that lies within
     the parity tolerance of zero is treated as ambiguous: the reward jumps there.  Also returns
     the magnitude scale of the reward's terms (sum of |term|), the scale rounding errors follow.
-    tol: the state tolerance x -> |dx| deciding the ambiguity (default contract (i))."""
-    _tol = tol or globals()["_tol"]
-    h = np.asarray(heli, dtype=np.float64)
-    d = np.asarray(dots, dtype=np.float64)
-    pn, pdn = h[:, 9:12] * n_t, d[:, 9:12] * n_t ** 2
-    pf = -(pn ** 2).sum(axis=1)
-    pt_lo, pt_hi = _terminal_bounds(pn, _tol(h[:, 9:12]) * n_t, pdn)
-    if task == "hover":
-        tgt = (np.array([0.0, 0.0, -sea_alt], np.float32) / np.float32(n_x)).astype(np.float64)  # fp32 (:33)
-        e = h[:, 15:18] / n_x - tgt
-        xf = -(e ** 2).sum(axis=1)
-        xt_lo, xt_hi = _terminal_bounds(e, _tol(h[:, 15:18]) / n_x, d[:, 15:18] / n_v)
-        lo = (np.maximum(pf, pt_lo) + np.maximum(xf, xt_lo)) / 2
-        hi = (np.maximum(pf, pt_hi) + np.maximum(xf, xt_hi)) / 2
-        scale = (np.abs(pf) + np.abs(pdn).sum(axis=1) + np.abs(xf) + np.abs(d[:, 15:18] / n_v).sum(axis=1)) / 2
-        return lo, hi, scale
-    v = np.sqrt((h[:, 6:9] ** 2).sum(axis=1))
-    ev = v / n_v - vel / n_v
-    vdn = (h[:, 6:9] * d[:, 6:9]).sum(axis=1) / v / n_a
-    vf = -ev ** 2
-    vt_lo, vt_hi = _terminal_bounds(ev[:, None], (_tol(v) / n_v)[:, None], vdn[:, None])
-    ed = h[:, 17] / n_x - float(np.float32(-sea_alt) / np.float32(n_x))   # fp32 target (:88)
-    df = -ed ** 2
-    dt_lo, dt_hi = _terminal_bounds(ed[:, None], (_tol(h[:, 17]) / n_x)[:, None], (d[:, 17] / n_v)[:, None])
-    lo = (np.maximum(pf, pt_lo) + np.maximum(vf, vt_lo) + np.maximum(df, dt_lo)) / 3
-    hi = (np.maximum(pf, pt_hi) + np.maximum(vf, vt_hi) + np.maximum(df, dt_hi)) / 3
-    scale = (np.abs(pf) + np.abs(pdn).sum(axis=1) + np.abs(vf) + np.abs(vdn) + np.abs(df)
-             + np.abs(d[:, 17] / n_v)) / 3
-    return lo, hi, scale
+    tol: the state tolerance x -> |dx| deciding the ambiguity (default contract (i)).
+    north_loc, east_loc, sea_alt, vel: the target, scalars or one value per row."""
+    t = task_terms(heli, dots, task, n_t, n_x, n_v, n_a, north_loc, east_loc, sea_alt, vel, tol)
+    lo = hi = scale = 0.0
+    with np.errstate(all="ignore"):
+        for g, cols in enumerate(t["groups"]):
+            c = list(cols)
+            t_lo, t_hi = _terminal_bounds(t["args"][:, c], t["arg_tol"][:, c], t["terms"][:, c])
+            f = t["final"][:, g]
+            lo = lo + _pymax(f, t_lo)
+            hi = hi + _pymax(f, t_hi)
+            scale = scale + _mag(f) + _mag(t["terms"][:, c]).sum(axis=1)
+    k = len(t["groups"])
+    return lo / k, hi / k, scale / k
 
 
 CONTACT_GR_ALT = 10.0   # ft: below this ground altitude the landing gear can be in contact
@@ -170,6 +210,92 @@ def f8_episodes():
 
 
 VARIANTS = ("turb5", "turb7_wind", "turb0", "heavy", "wing")
+
+TASK_FIELDS = {"hover": ("north_loc", "east_loc", "sea_alt"), "forward_flight": ("vel", "sea_alt")}
+
+
+def _edge_tol(x):
+    """The ambiguity of a sign() argument on the edge rows of task_kats.npz, whose inputs are exact fp32 values:
+    only the arithmetic differs.  An argument is a difference of two operands of the state value's magnitude
+    over a normaliser; the fp32 forms round the normaliser's reciprocal, the product and the target quotient
+    (half an ulp each), the reference rounds its target and quotient to fp32 too, and sqrt of the speed adds
+    two more: under 4 ulp of the operand, which 8 ulp of the state value covers (ulp(x) / n >= ulp(x / n) / 2)."""
+    with np.errstate(all="ignore"):
+        return 8.0 * np.spacing(np.abs(np.asarray(x, dtype=np.float64)).astype(np.float32)).astype(np.float64)
+
+
+def load_task_kats(task):
+    """task_kats.npz for one task: heli, dots [n,18] float64 (fp32 values), target {field: [n]}, reward,
+    success_step, label ("" on clear rows), clear (mask), candidates, dropped."""
+    d = _npz(os.path.join(GOLDEN, "task_kats.npz"))
+    row = d[f"{task}/row"].astype(np.int64)
+    out = {"heli": d["heli"][row].astype(np.float64), "dots": d["dots"][row].astype(np.float64),
+           "target": {f: d[f"{task}/target"][:, j].copy() for j, f in enumerate(TASK_FIELDS[task])},
+           "reward": d[f"{task}/reward"], "success_step": d[f"{task}/success_step"],
+           "label": np.array([str(s) for s in d[f"{task}/label"]]),
+           "candidates": int(d[f"{task}/candidates"]), "dropped": int(d[f"{task}/dropped"])}
+    out["clear"] = out["label"] == ""
+    return out
+
+
+def task_bounds(k, task, rows=None):
+    """reward_bounds of task_kats rows under each row's own target: contract (i) ambiguity on clear rows (none
+    is ambiguous there), _edge_tol on edge rows.  (lo, hi, reward tolerance)."""
+    rows = np.arange(len(k["reward"])) if rows is None else rows
+    lo, hi, rt = np.empty(len(rows)), np.empty(len(rows)), np.empty(len(rows))
+    for mask, tol in ((k["clear"][rows], None), (~k["clear"][rows], _edge_tol)):
+        if not mask.any():
+            continue
+        r = rows[mask]
+        a, b, s = reward_bounds(k["heli"][r], k["dots"][r], task, tol=tol, **{f: v[r] for f, v in k["target"].items()})
+        lo[mask], hi[mask], rt[mask] = a, b, REWARD_ABS + REWARD_REL * s
+    return lo, hi, rt
+
+
+def check_task_kats(k, task, reward, success, who):
+    """The assertions every evaluator of the task layer meets on task_kats.npz: clear rows within the reward
+    contract of the reference, edge rows inside the sign-ambiguity bounds, NaN where and only where the
+    reference's reward is, success_step equal but on the rows built to sit within tolerance of -1.  Returns the
+    worst error / tolerance over the finite rows."""
+    reward = np.asarray(reward, dtype=np.float64)
+    ref = k["reward"]
+    bad = np.nonzero(np.isnan(reward) != np.isnan(ref))[0]
+    assert len(bad) == 0, (who, task, "isnan", [(k["label"][i], reward[i], ref[i]) for i in bad[:10]])
+    lo, hi, rt = task_bounds(k, task)
+    fin = ~np.isnan(ref)
+    with np.errstate(all="ignore"):
+        clear = k["clear"] & fin
+        err = np.where(clear, np.abs(reward - ref), np.maximum(np.maximum(lo - reward, reward - hi), 0.0))
+        ratio = np.where(fin, err / rt, 0.0)
+    bad = np.nonzero(~(ratio <= 1.0))[0]
+    assert len(bad) == 0, (who, task, [(i, k["label"][i], reward[i], ref[i], lo[i], hi[i], rt[i]) for i in bad[:10]])
+    near = np.array([s.startswith("near_minus_one") for s in k["label"]])
+    bad = np.nonzero((np.asarray(success).astype(bool) != k["success_step"]) & ~near)[0]
+    assert len(bad) == 0, (who, task, "success_step", [(i, k["label"][i]) for i in bad[:10]])
+    return float(ratio.max())
+
+
+def load_task_traj():
+    """task_traj.npz as {scenario: {task, dt, max_time, action, eta, init_*, heli, dots (post-step rows with
+    the recorded columns filled in, the rest 0), targets: {name: {target: {field: value}, reward, flags...}}}}."""
+    d = _npz(os.path.join(GOLDEN, "task_traj.npz"))
+    cols = d["cols"]
+    out = {}
+    for s in (str(x) for x in d["scenarios"]):
+        task = str(d[f"{s}/task"])
+        T = len(d[f"{s}/action"])
+        e = {"task": task, "dt": float(d["dt"]), "max_time": float(d["max_time"]), "heli": np.zeros((T, 18)),
+             "dots": np.zeros((T, 18)), "targets": {}}
+        e["heli"][:, cols], e["dots"][:, cols] = d[f"{s}/state_cols"], d[f"{s}/dots_cols"]
+        for key in ("action", "eta", "init_state", "init_wind_state", "init_obs", "init_state_dots", "init_trim_cond"):
+            e[key] = d[f"{s}/{key}"]
+        for t in (str(x) for x in d[f"{s}/targets"]):
+            g = {key: d[f"{s}/{t}/{key}"] for key in ("reward", "success_step", "failed", "successed", "time_up",
+                                                      "terminated", "truncated")}
+            g["target"] = dict(zip(TASK_FIELDS[task], map(float, d[f"{s}/{t}/target"])))
+            e["targets"][t] = g
+        out[s] = e
+    return out
 
 
 def load_contact(dt):

@@ -27,8 +27,15 @@ reset_f8.npz     second-episode resets (F8): the reference re-trims against the 
                  last step (helicopter.py:198, helicopter_dynamics.py:66-71,491-555) -- winds,
                  reset states for several trim conditions / dt, and terminal steps of episodes
                  that end by a crash followed by the reset the reference computes.
+task_kats.npz    the reference's HeliHover / HeliForwardFlight._calculate_reward on rows of (heli state,
+                 state_dots, target): post-step rows of the recorded scenarios under targets away from the
+                 defaults (kept only where no sign() argument and no success threshold is within tolerance),
+                 and a fixed list of named edge rows (at the target, zeros, NaN, inf, ties, near -1).
+task_traj.npz    short episodes (dt 0.01, max_time 2.0) that end by `successed` or `time_up` under several
+                 targets, with the flags of Heli.step per step.
 
-Usage: python tools/gen_goldens.py [--only f8]   (numpy 2.2.6 promotion rules are part of the result)
+Usage: python tools/gen_goldens.py [--only f8|contact|variants|variant:<v>|task]
+(numpy 2.2.6 promotion rules are part of the result; --only task reads the committed trajectory fixtures)
 """
 import json
 import os
@@ -521,10 +528,321 @@ def run_scenario(ns, dt, name, cond, kind, max_steps, seed, env=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# The task layer away from the default targets: task_kats.npz and task_traj.npz (--only task)
+
+TASK_CLS = {"hover": "HeliHover", "forward_flight": "HeliForwardFlight"}
+TASK_FIELDS = {"hover": ("north_loc", "east_loc", "sea_alt"), "forward_flight": ("vel", "sea_alt")}
+# post-step (state, state_dots) rows of the recorded scenarios: (file, fractions of each scenario's length)
+TASK_ROW_SOURCES = [("traj_dt0.02.npz", (0.1, 0.35, 0.6, 1.0)), ("traj_dt0.01.npz", (0.2, 0.55, 1.0)),
+                    ("traj_contact.npz", (0.5, 0.97, 1.0))]
+
+
+def _gc():
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import golden_cases
+    return golden_cases
+
+
+def _task_env(ns, task):
+    env = getattr(ns.tasks, TASK_CLS[task])()
+    env.task_target = {}    # this env's own dict (Heli.set_target updates one shared by every instance)
+    return env
+
+
+def _task_eval(ns, env, task, heli, dots, target):
+    """The reference's _calculate_reward on a given post-step state: heli_dyn.state and state_dots set
+    directly, as float64 arrays like the ones Heli.step leaves (dynamics.py:168-169)."""
+    env.heli_dyn.state.val = np.array(heli, dtype=np.float64)
+    env.heli_dyn.state_dots.val = np.array(dots, dtype=np.float64)
+    env.task_target = {"heading": 0, **{k: float(v) for k, v in target.items()}}
+    with np.errstate(all="ignore"):
+        r, s = getattr(ns.tasks, TASK_CLS[task])._calculate_reward(env)
+    return float(r), bool(s)
+
+
+def _task_rows():
+    """(name, heli[18], dots[18]) rounded to fp32 values, from the committed trajectories."""
+    rows = []
+    for fname, fracs in TASK_ROW_SOURCES:
+        with np.load(os.path.join(OUT, fname), allow_pickle=False) as d:
+            for n in d["scenarios"]:
+                st, dd = d[f"{n}/state"], d[f"{n}/state_dots"]
+                for t in sorted({int(round(f * (len(st) - 1))) for f in fracs}):
+                    rows.append((f"{fname[:-4]}/{n}/{t}", st[t].astype(np.float32).astype(np.float64),
+                                 dd[t].astype(np.float32).astype(np.float64)))
+    return rows
+
+
+def _hover_targets(h):
+    n, e, a = float(h[15]), float(h[16]), float(-h[17])
+    off = [(30.0, 4.0, -3.0), (-42.0, -5.0, 4.0), (3.0, 42.0, -4.0), (-4.0, -30.0, 3.0), (4.0, -3.0, 30.0),
+           (-3.0, 5.0, -42.0)]   # (north, east, up): each axis on both sides of the 36 ft success radius
+    out = [(0.0, 0.0, 4000.0), (n, e, a)] + [(n + x, e + y, a + z) for x, y, z in off]
+    out += [(-400.0, 90.0, 3000.0), (n + 10.1, e - 7.3, 1546.37), (1546.37, -20.7, a + 12.3)]
+    return [dict(zip(TASK_FIELDS["hover"], t)) for t in out]
+
+
+def _forward_targets(h):
+    v, a = float(np.sqrt((h[6:9] ** 2).sum())), float(-h[17])
+    out = [(100.0, 4000.0), (40.0, a + 30.0), (80.0, a - 42.0), (160.0, 3000.0), (v, a), (v + 25.0, a - 30.0),
+           (v - 25.0, a + 42.0), (v + 45.0, a + 30.5), (v - 45.0, a - 30.5), (100.37, 4100.0), (80.0, 1546.37)]
+    # hg_set_goals refuses vel <= 0 (the reference would take it): such a pair is no candidate
+    return [dict(zip(TASK_FIELDS["forward_flight"], t)) for t in out if t[0] > 1.0]
+
+
+def _clear(gc, task, heli, dots, target):
+    """No sign() argument within contract (i) of zero and every final term clear of -1 by the reward
+    tolerance of the row."""
+    t = gc.task_terms(heli[None], dots[None], task, **target)
+    _, _, scale = gc.reward_bounds(heli[None], dots[None], task, **target)
+    rt = gc.REWARD_ABS + gc.REWARD_REL * scale[0]
+    return bool(np.all(np.abs(t["args"]) > t["arg_tol"]) and np.all(np.abs(t["final"] + 1.0) > rt))
+
+
+def _edge_rows(base):
+    """The fixed, named edge rows: (label, task, heli, dots, target).  `base`: a free-flight row."""
+    f32 = lambda x: float(np.float32(x))  # noqa: E731
+    h0, d0 = base
+    n, e, a = float(h0[15]), float(h0[16]), float(-h0[17])
+    v = float(np.sqrt((h0[6:9] ** 2).sum()))
+    n_t, n_v = np.sqrt(2 * 18 / 32.2), np.sqrt(2 * 18 * 32.2)
+    near = {"north_loc": n + 10.0, "east_loc": e - 12.0, "sea_alt": a + 8.0}
+    ff = {"vel": v + 20.0, "sea_alt": a + 8.0}
+    rows = []
+
+    def add(label, task, target, hs=None, ds=None):
+        h, d = h0.copy(), d0.copy()
+        for k, val in (hs or {}).items():
+            h[k] = val
+        for k, val in (ds or {}).items():
+            d[k] = val
+        rows.append((label, task, h, d, dict(target)))
+
+    add("at_target_north", "hover", dict(near, north_loc=n))
+    add("at_target_east", "hover", dict(near, east_loc=e))
+    add("at_target_alt", "hover", dict(near, sea_alt=a))
+    add("at_target_all", "hover", {"north_loc": n, "east_loc": e, "sea_alt": a})
+    # a position whose quotient by n_x is exact in fp32: the reference's argument is then exactly 0
+    add("at_target_all_exact", "hover", {"north_loc": 72.0, "east_loc": -180.0, "sea_alt": 3996.0},
+        {15: 72.0, 16: -180.0, 17: -3996.0})
+    add("at_target_alt", "forward_flight", dict(ff, sea_alt=a))
+    add("at_target_vel", "forward_flight", dict(ff, vel=v))
+    add("at_target_all", "forward_flight", {"vel": v, "sea_alt": a})
+    for task, tg in (("hover", near), ("forward_flight", ff)):
+        add("pqr_zero", task, tg, {9: 0.0, 10: 0.0, 11: 0.0})
+        add("pqr_negzero", task, tg, {9: -0.0, 10: -0.0, 11: -0.0})
+        add("p_zero_only", task, tg, {9: 0.0})
+        add("nan_pqr", task, tg, {10: np.nan})
+        add("nan_pqrdot", task, tg, None, {9: np.nan})
+        add("nan_xyz", task, tg, {17: np.nan})
+        add("nan_xyzdot", task, tg, None, {17: np.nan})
+        add("nan_uvw", task, tg, {7: np.nan})
+        add("nan_uvwdot", task, tg, None, {6: np.nan})
+        add("inf_alt", task, tg, {17: -np.inf})
+        add("neginf_alt", task, tg, {17: np.inf})
+        # (p n_t)^2 = pdot n_t^2 with powers of two: final == terminal in the reference's fp64
+        add("tie_pqr", task, tg, {9: 0.5, 10: 0.0, 11: 0.0}, {9: 0.25, 10: 0.0, 11: 0.0})
+        for sgn, name in ((1.0, "inside"), (-1.0, "outside")):
+            add(f"near_minus_one_pqr_{name}", task, tg, {9: f32((1.0 - sgn * 1e-5) / n_t), 10: 0.0, 11: 0.0})
+    add("nan_north", "hover", near, {15: np.nan})
+    add("inf_north", "hover", near, {15: np.inf})
+    add("nan_xdot_north", "hover", near, None, {15: np.nan})
+    add("uvw_zero", "forward_flight", ff, {6: 0.0, 7: 0.0, 8: 0.0})
+    add("uvw_zero_default_target", "forward_flight", {"vel": 100.0, "sea_alt": 4000.0}, {6: 0.0, 7: 0.0, 8: 0.0})
+    # e = 0.5 on one axis, 0 on the others (exact quotients): final = -0.25 against xdot / n_v
+    add("tie_xyz", "hover", {"north_loc": 72.0, "east_loc": -180.0, "sea_alt": 3996.0},
+        {15: 90.0, 16: -180.0, 17: -3996.0}, {15: f32(0.25 * n_v), 16: 0.0, 17: 0.0})
+    add("tie_vel", "forward_flight", {"vel": f32(v - 0.5 * n_v), "sea_alt": a + 8.0}, None,
+        {6: f32(d0[6] + (0.25 * 32.2 * v - float((h0[6:9] * d0[6:9]).sum())) / h0[6])})
+    for sgn, name in ((1.0, "inside"), (-1.0, "outside")):
+        add(f"near_minus_one_xyz_{name}", "hover", dict(near, north_loc=n, east_loc=e, sea_alt=a),
+            {15: f32(n + 36.0 * (1.0 - sgn * 3e-5))})
+        add(f"near_minus_one_alt_{name}", "forward_flight", dict(ff, sea_alt=a), {17: f32(-a - 36.0 * (1.0 - sgn * 3e-5))})
+        add(f"near_minus_one_vel_{name}", "forward_flight", dict(ff, vel=f32(v + n_v * (1.0 - sgn * 3e-5))))
+    return rows
+
+
+def gen_task_kats(ns):
+    """task_kats.npz: HeliHover / HeliForwardFlight._calculate_reward on rows of (heli state, state_dots,
+    target).  heli [S,18] and dots [S,18] float32 (every input an fp32 value); per task `<task>/row`
+    (index into heli/dots), `<task>/target` (float64, columns TASK_FIELDS), `<task>/reward`,
+    `<task>/success_step`, `<task>/label` ("" on clear rows, the edge's name otherwise),
+    `<task>/candidates` and `<task>/dropped` (the clear (row, target) candidates, and those of them
+    dropped as ambiguous)."""
+    gc = _gc()
+    rows = _task_rows()
+    states = [(h, d) for _, h, d in rows]
+    out = {"row_name": np.array([n for n, _, _ in rows])}
+    # the direct evaluation is the reference's step-time one: an unrounded recorded row gives the recorded reward
+    with np.load(os.path.join(OUT, "traj_dt0.02.npz"), allow_pickle=False) as d:
+        for task, key in (("hover", "reward_hover"), ("forward_flight", "reward_ff")):
+            env = _task_env(ns, task)
+            for n in d["scenarios"]:
+                for t in (0, len(d[f"{n}/state"]) - 1):
+                    r, _ = _task_eval(ns, env, task, d[f"{n}/state"][t], d[f"{n}/state_dots"][t],
+                                      {"north_loc": 0, "east_loc": 0, "sea_alt": 4000, "vel": 100})
+                    assert r == float(d[f"{n}/{key}"][t]), (task, n, t, r)
+    base = next((h, d) for n, h, d in rows if n.startswith("traj_dt0.02/forward80/") and not n.endswith("/0"))
+    edges = _edge_rows(base)
+    for task, targets in (("hover", _hover_targets), ("forward_flight", _forward_targets)):
+        env = _task_env(ns, task)
+        rec = {k: [] for k in ("row", "target", "reward", "success_step", "label")}
+        cand = dropped = 0
+        for i, (h, d) in enumerate(states[:len(rows)]):   # (the edge rows follow them)
+            for tg in targets(h):
+                cand += 1
+                if not _clear(gc, task, h, d, tg):
+                    dropped += 1
+                    continue
+                r, s = _task_eval(ns, env, task, h, d, tg)
+                assert np.isfinite(r)
+                for k, v in zip(rec, (i, [tg[f] for f in TASK_FIELDS[task]], r, s, "")):
+                    rec[k].append(v)
+        for label, etask, h, d, tg in edges:
+            if etask != task:
+                continue
+            assert np.array_equal(h.astype(np.float32).astype(np.float64), h, equal_nan=True)
+            assert np.array_equal(d.astype(np.float32).astype(np.float64), d, equal_nan=True)
+            states.append((h, d))
+            r, s = _task_eval(ns, env, task, h, d, tg)
+            for k, v in zip(rec, (len(states) - 1, [tg[f] for f in TASK_FIELDS[task]], r, s, label)):
+                rec[k].append(v)
+        print(f"task kats {task}: {cand} candidates, {dropped} dropped as ambiguous, "
+              f"{sum(1 for x in rec['label'] if x)} edge rows", flush=True)
+        out[f"{task}/row"] = np.array(rec["row"], dtype=np.int16)
+        out[f"{task}/target"] = np.array(rec["target"], dtype=np.float64)
+        out[f"{task}/reward"] = np.array(rec["reward"], dtype=np.float64)
+        out[f"{task}/success_step"] = np.array(rec["success_step"], dtype=bool)
+        out[f"{task}/label"] = np.array(rec["label"])
+        out[f"{task}/candidates"] = np.array(cand)
+        out[f"{task}/dropped"] = np.array(dropped)
+    out["heli"] = np.array([h for h, _ in states], dtype=np.float32)
+    out["dots"] = np.array([d for _, d in states], dtype=np.float32)
+    return out
+
+
+TASK_TRAJ_DT, TASK_TRAJ_MAX_TIME = 0.01, 2.0
+TASK_COLS = [6, 7, 8, 9, 10, 11, 15, 16, 17]
+
+
+def _task_episode(ns, task, cond, target, seed):
+    """One reference episode with the trim action until it ends: Heli.step's own outputs per step."""
+    ns.helicopter.DT = TASK_TRAJ_DT
+    env = getattr(ns.tasks, TASK_CLS[task])()
+    env.set_max_time(TASK_TRAJ_MAX_TIME)
+    env.set_trim_cond(cond)
+    np.random.seed(seed)
+    obs0, _ = env.reset()
+    init = {"state": np.asarray(env.heli_dyn.state.val, dtype=np.float64),
+            "wind_state": np.asarray(env.wind_dyn.state.val, dtype=np.float64),
+            "obs": np.asarray(obs0, dtype=np.float64),
+            "state_dots": np.asarray(env.heli_dyn.state_dots.val, dtype=np.float64),
+            "trim_action": np.asarray(env.heli_dyn.action, dtype=np.float64), "trim_cond": trim_vec(cond)}
+    x = init["state"]
+    own = {"north_loc": float(x[15]), "east_loc": float(x[16]), "sea_alt": float(-x[17])}
+    tg = target(own)
+    env.task_target = {"heading": 0, **tg}
+    a = np.asarray(env.heli_dyn.action, dtype=np.float32)
+    rec = {k: [] for k in ("action", "eta", "state", "state_dots", "obs", "reward", "success_step", "failed", "successed",
+                           "time_up", "terminated", "truncated")}
+    for _ in range(1000):
+        obs, rew, term, trunc, info = env.step(a.copy())
+        _, s = getattr(ns.tasks, TASK_CLS[task])._calculate_reward(env)
+        for k, v in zip(rec, (a.astype(np.float64), np.asarray(env.wind_dyn.eta, dtype=np.float64),
+                              np.asarray(env.heli_dyn.state.val, dtype=np.float64),
+                              np.asarray(env.heli_dyn.state_dots.val, dtype=np.float64), np.asarray(obs, dtype=np.float64),
+                              float(rew), bool(s), bool(info["failed"]), bool(info["successed"]), bool(info["time_up"]),
+                              bool(term), bool(trunc))):
+            rec[k].append(v)
+        if term or trunc:
+            break
+    return init, tg, {k: np.array(v) for k, v in rec.items()}
+
+
+# name -> (task, trim overrides, [(target name, target from the trim position, how the episode must end)])
+TASK_TRAJ = {
+    "hover": ("hover", {}, [
+        ("trim", lambda o: dict(o), "successed"),
+        ("north30", lambda o: dict(o, north_loc=o["north_loc"] + 30.0), "successed"),
+        ("north42", lambda o: dict(o, north_loc=o["north_loc"] + 42.0), "time_up"),
+        ("up30", lambda o: dict(o, sea_alt=o["sea_alt"] + 30.0), "successed"),
+        ("default", lambda o: {"north_loc": 0.0, "east_loc": 0.0, "sea_alt": 4000.0}, "time_up")]),
+    "forward80": ("forward_flight", {"ned_vel": [80.0, 0.0, 0.0]}, [
+        ("vel80", lambda o: {"vel": 80.0, "sea_alt": o["sea_alt"]}, "successed"),
+        ("vel100", lambda o: {"vel": 100.0, "sea_alt": o["sea_alt"]}, "successed"),
+        ("vel80_up42", lambda o: {"vel": 80.0, "sea_alt": o["sea_alt"] + 42.0}, "time_up")]),
+}
+
+
+def gen_task_traj(ns):
+    """task_traj.npz: short reference episodes (dt 0.01, max_time 2.0, trim action) that end through the task
+    layer.  Per scenario one physics trajectory (`<s>/action`, eta, init_*, and columns `cols` of the post-step
+    state and state_dots as state_cols, dots_cols: the longest episode's, the others are its prefixes) and per target `<s>/<target>/{target, reward, success_step, failed,
+    successed, time_up, terminated, truncated}` up to and including the ending step."""
+    gc = _gc()
+    out = {"dt": np.array(TASK_TRAJ_DT), "max_time": np.array(TASK_TRAJ_MAX_TIME)}
+    for i, (name, (task, cond, targets)) in enumerate(TASK_TRAJ.items()):
+        longest = None
+        for tname, tfn, ending in targets:
+            init, tg, rec = _task_episode(ns, task, cond, tfn, seed=500 + i)
+            T = len(rec["reward"])
+            assert rec["terminated"][-1] or rec["truncated"][-1], (name, tname)
+            assert not (rec["terminated"][:-1].any() or rec["truncated"][:-1].any())
+            assert not rec["failed"].any(), (name, tname)
+            if ending == "successed":
+                assert rec["successed"][-1] and not rec["time_up"][-1], (name, tname, T)
+            else:
+                assert rec["time_up"][-1] and not rec["successed"][-1], (name, tname, T)
+            # every final term clear of -1 by the trajectory tolerance: success flags compare exactly
+            t = gc.task_terms(rec["state"], rec["state_dots"], task, tol=gc._traj_tol, **tg)
+            _, _, scale = gc.reward_bounds(rec["state"], rec["state_dots"], task, tol=gc._traj_tol, **tg)
+            margin = np.abs(t["final"] + 1.0) / (gc.TRAJ_ABS + gc.TRAJ_REL * scale)[:, None]
+            assert margin.min() > 1.0, (name, tname, margin.min())
+            print(f"task traj {name}/{tname}: {T} steps, ends by {ending}, least |final + 1| / tol {margin.min():.1f}",
+                  flush=True)
+            if longest is None or T > len(longest[1]["reward"]):
+                longest = (init, rec)
+            for k in ("reward", "success_step", "failed", "successed", "time_up", "terminated", "truncated"):
+                out[f"{name}/{tname}/{k}"] = rec[k]
+            out[f"{name}/{tname}/target"] = np.array([tg[f] for f in TASK_FIELDS[task]], dtype=np.float64)
+            out[f"{name}/{tname}/physics"] = (rec["state"], rec["eta"])
+        init, rec = longest
+        for tname, _, _ in targets:   # one physics trajectory: the noise and the state do not see the target
+            st, eta = out.pop(f"{name}/{tname}/physics")
+            assert np.array_equal(st, rec["state"][:len(st)]) and np.array_equal(eta, rec["eta"][:len(eta)])
+        out[f"{name}/action"], out[f"{name}/eta"] = rec["action"], rec["eta"]
+        # the columns the task layer reads (uvw, pqr, xyz), to keep the file small
+        out[f"{name}/state_cols"] = rec["state"][:, TASK_COLS]
+        out[f"{name}/dots_cols"] = rec["state_dots"][:, TASK_COLS]
+        out.update({f"{name}/init_{k}": v for k, v in init.items()})
+        out[f"{name}/task"] = np.array(task)
+        out[f"{name}/targets"] = np.array([t[0] for t in targets])
+    out["scenarios"] = np.array(list(TASK_TRAJ))
+    out["cols"] = np.array(TASK_COLS)
+    return out
+
+
+def write_task_fixtures(ns, meta):
+    """task_kats.npz and task_traj.npz (they read the trajectory fixtures, so those come first), and their
+    entry in META.json."""
+    np.savez_compressed(os.path.join(OUT, "task_kats.npz"), **gen_task_kats(ns))
+    np.savez_compressed(os.path.join(OUT, "task_traj.npz"), **gen_task_traj(ns))
+    meta["task_fixtures"] = {"files": ["task_kats.npz", "task_traj.npz"], "switch": "--only task",
+                             "numpy": np.__version__}
+    with open(os.path.join(OUT, "META.json"), "w") as f:
+        json.dump(meta, f, indent=1)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ns = refload.load()
     only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
+    if only == "task":
+        with open(os.path.join(OUT, "META.json")) as f:
+            meta = json.load(f)
+        write_task_fixtures(ns, meta)
+        return
     if only in (None, "f8"):
         np.savez_compressed(os.path.join(OUT, "reset_f8.npz"), **gen_f8(ns))
     if only in (None, "contact"):
@@ -552,8 +870,7 @@ def main():
         out["scenarios"] = np.array(names)
         out["dt"] = np.array(dt)
         np.savez_compressed(os.path.join(OUT, f"traj_dt{tag}.npz"), **out)
-    with open(os.path.join(OUT, "META.json"), "w") as f:
-        json.dump(meta, f, indent=1)
+    write_task_fixtures(ns, meta)
 
 
 if __name__ == "__main__":
