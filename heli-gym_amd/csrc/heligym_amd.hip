@@ -849,6 +849,33 @@ __global__ __launch_bounds__(kBlock) void task_kernel(const float* heli, const f
     success[i] = ok ? 1 : 0;
 }
 
+// hg_debug_failed: the failure test alone (hg::is_failed, the function the step kernels call, and its clause bits
+// from hg::failed_clauses) on given rows of
+// post-step state and k4 derivatives, with the handle's constants and terrain texels; under a fleet, row i with
+// the constants of the class of env i % n_envs.
+static_assert(hg::kFailContact == HG_FAIL_CONTACT && hg::kFailSink == HG_FAIL_SINK && hg::kFailRoll == HG_FAIL_ROLL &&
+                  hg::kFailPitch == HG_FAIL_PITCH && hg::kFailNS == HG_FAIL_NS && hg::kFailEW == HG_FAIL_EW &&
+                  hg::kFailCeiling == HG_FAIL_CEILING && hg::kFailFailed == HG_FAIL_FAILED,
+              "physics.h's clause bits are the header's HG_FAIL_*");
+__global__ __launch_bounds__(kBlock) void failed_kernel(const float* heli, const float* dots, int64_t n,
+                                                        const Params<float>* Pp, const float2* hmap,
+                                                        const Params<float>* table, const int32_t* tile_class,
+                                                        int64_t n_envs, uint8_t* failed, uint8_t* clauses) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const Params<float>& P = table ? table[tile_class[(i % n_envs) / kTileEnvs]] : *Pp;
+    float s[18], d[18];
+#pragma unroll
+    for (int k = 0; k < 18; ++k) {
+        s[k] = heli[18 * i + k];
+        d[k] = dots[18 * i + k];
+    }
+    // (a NaN or far-off position lands in a clamped cell: map_coord's clamp, as in the step)
+    const hg::Ground<float> g = hg::ground_height(P, hmap, s[15], s[16]);
+    failed[i] = hg::is_failed(P, s, d, g) ? 1 : 0;
+    clauses[i] = (uint8_t)hg::failed_clauses(P, s, d, g);
+}
+
 // hg_set_policy: the caller's weights into the handle's packed image, each matrix element where the
 // lane that uses it as a matrix operand loads it from (layout: policy_mlp.h).  The value head's
 // elements are not written (value_pack_kernel's), so a head set before or after stays.
@@ -1047,6 +1074,12 @@ int32_t first_step_above(double dt, double thr, bool strict) {
     return INT32_MAX;
 }
 
+// The largest fp32 value not above x (x finite): for an fp32 v, v > x in fp64 exactly when v > f32_not_above(x).
+static float f32_not_above(double x) {
+    const float f = (float)x;
+    return (double)f > x ? nextafterf(f, -INFINITY) : f;
+}
+
 template <typename R>
 Params<R> derive(const hg_config& c, int rows, int cols) {
     const hg_airframe& a = c.af;
@@ -1147,8 +1180,10 @@ Params<R> derive(const hg_config& c, int rows, int cols) {
     P.hm_cy = (R)(cols / 2);
     P.hm_rows = rows;
     P.hm_cols = cols;
-    P.ns_half = (R)(a.env_NS_MAX / 2);
-    P.ew_half = (R)(a.env_EW_MAX / 2);
+    // (float32 state against a python float compares in float32 under NumPy 2: the threshold rounded to fp32,
+    // in the fp64 form too -- fail_ang below likewise)
+    P.ns_half = (R)(float)(a.env_NS_MAX / 2);
+    P.ew_half = (R)(float)(a.env_EW_MAX / 2);
     // wind (wind_dynamics.py:21-28, 56)
     // (weather.h: the same function forms a per-env weather's record, hg_set_weather)
     hgw::set_wind(P, hgw::wind_constants<R>(a.env_WIND_DIR_deg, a.env_WIND_SPD, (double)a.env_TURB_LVL));
@@ -1189,8 +1224,11 @@ Params<R> derive(const hg_config& c, int rows, int cols) {
     P.tgt_n[2] = (R)(-c.target.sea_alt / n_x);
     P.vel_tgt_n = (R)(c.target.vel / n_v);
     P.dwn_tgt_n = (R)(-c.target.sea_alt / n_x);
-    P.fail_zdot = (R)(mr_VT * 0.05);
-    P.fail_ang = (R)(60 * kD2R);
+    // _is_failed's thresholds (helicopter.py:228-230) under NumPy 2's promotion: state_dots is float64, so the sink
+    // rate compares in fp64 (an fp32 zdot is above V_TIP*0.05 exactly when it is above the largest fp32 not above
+    // it); euler is float32 at the reset-time test, so roll and pitch compare in float32 against fp32(60 deg)
+    P.fail_zdot = sizeof(R) == 4 ? (R)f32_not_above(mr_VT * 0.05) : (R)(mr_VT * 0.05);
+    P.fail_ang = (R)(float)(60 * kD2R);
     P.task = c.task;
     P.time_up_steps = first_step_above(dt, c.max_time, true);
     P.success_steps = first_step_above(dt, c.max_time / 4, false);
@@ -3690,6 +3728,22 @@ int32_t hg_debug_task_host(const hg_config* cfg, const double* heli, const doubl
     return HG_OK;
 }
 
+int32_t hg_debug_failed_host(const hg_config* cfg, const double* terrain_ft, int32_t rows, int32_t cols, const double* heli,
+                             const double* dots, int64_t n, uint8_t* failed, uint8_t* clauses) {
+    if (!cfg || !terrain_ft || n < 0 || (n > 0 && (!heli || !dots || !failed || !clauses)))
+        return fail(HG_E_INVALID, "hg_debug_failed_host: bad arguments");
+    if (int32_t rc = check_config(cfg, rows, cols)) return rc;
+    const Params<double> P = derive<double>(*cfg, rows, cols);
+    const std::vector<float2> hmap = split_terrain(terrain_ft, rows, cols);
+    for (int64_t i = 0; i < n; ++i) {
+        const double *s = heli + 18 * i, *d = dots + 18 * i;
+        const hg::Ground<double> g = hg::ground_height<double>(P, hmap.data(), s[15], s[16]);
+        failed[i] = hg::is_failed<double>(P, s, d, g) ? 1 : 0;
+        clauses[i] = (uint8_t)hg::failed_clauses<double>(P, s, d, g);
+    }
+    return HG_OK;
+}
+
 int32_t hg_goal_draw(const hg_config* cfg, const hg_goal_box* box, int64_t global_env, int32_t episode, hg_target* out,
                      float rec[8]) {
     if (!cfg || !box) return fail(HG_E_INVALID, "hg_goal_draw: NULL argument");
@@ -4053,6 +4107,20 @@ int32_t hg_debug_task(hg_env* e, const float* heli, const float* dots, float* re
     if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
     hipLaunchKernelGGL(task_kernel, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, heli, dots, n, e->cfg.task,
                        PARAM_ARG(e), e->goals ? e->goal_rec : nullptr, e->n, reward, success);
+    HIP_TRY(hipGetLastError());
+    return HG_OK;
+}
+
+int32_t hg_debug_failed(hg_env* e, const float* heli, const float* dots, uint8_t* failed, uint8_t* clauses, int64_t n,
+                        void* stream) {
+    if (!e) return fail(HG_E_INVALID, "env is NULL");
+    if (n < 0 || (n > 0 && (!heli || !dots || !failed || !clauses))) return fail(HG_E_INVALID, "hg_debug_failed: bad arguments");
+    if (n == 0) return HG_OK;
+    DevGuard dev_guard(e);
+    if (!dev_guard.ok) return fail(HG_E_HIP, "hipSetDevice to the handle's device failed");
+    hipLaunchKernelGGL(failed_kernel, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, heli, dots, n, PARAM_ARG(e),
+                       (const float2*)e->hmap, e->fleet ? e->fleet_table : nullptr, e->fleet ? e->fleet_tiles : nullptr, e->n,
+                       failed, clauses);
     HIP_TRY(hipGetLastError());
     return HG_OK;
 }

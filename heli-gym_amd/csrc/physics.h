@@ -968,4 +968,26 @@ HD bool is_failed(const Params<R>& P, const R s[18], const R d[18], const Ground
     return (hit && (c2 || c3 || c4)) || c5;
 }
 
+// The clauses of is_failed as bits (HG_FAIL_* in heligym_amd.h), for the diagnostics that report them: a clause
+// that holds sets its bit whether or not it fails the env (contact alone does not; roll and pitch are one-sided,
+// :229-230), and kFailFailed carries this function's own combination of them.  A copy: routing is_failed through
+// it moved instructions in the existing kernels.  The diagnostics return is_failed's result beside these bits and
+// the tests hold kFailFailed equal to it on every row.
+enum : uint32_t {
+    kFailContact = 1u, kFailSink = 2u, kFailRoll = 4u, kFailPitch = 8u, kFailNS = 16u, kFailEW = 32u, kFailCeiling = 64u,
+    kFailFailed = 128u
+};
+
+template <typename R>
+HD uint32_t failed_clauses(const Params<R>& P, const R s[18], const R d[18], const Ground<R>& gp) {
+    const R gta = gp.h() + P.wl_cg_ft;
+    const bool hit = -gp.zh(s[17]) - P.wl_cg_ft < (R)0;
+    const bool c2 = d[17] > P.fail_zdot;
+    const bool c3 = s[12] > P.fail_ang, c4 = s[13] > P.fail_ang;
+    const bool ns = m_fabs(s[15]) > P.ns_half, ew = m_fabs(s[16]) > P.ew_half, top = -s[17] > gta + (R)10000;
+    const bool f = (hit && (c2 || c3 || c4)) || (ns || ew || top);
+    return (hit ? kFailContact : 0u) | (c2 ? kFailSink : 0u) | (c3 ? kFailRoll : 0u) | (c4 ? kFailPitch : 0u) |
+           (ns ? kFailNS : 0u) | (ew ? kFailEW : 0u) | (top ? kFailCeiling : 0u) | (f ? kFailFailed : 0u);
+}
+
 }  // namespace hg

@@ -21,6 +21,8 @@ HG_COUNTER_COLS = 3
 HG_OK = 0
 HG_TASK_HELI, HG_TASK_HOVER, HG_TASK_FORWARD_FLIGHT = 0, 1, 2
 HG_INFO_FAILED, HG_INFO_SUCCESSED, HG_INFO_TIME_UP, HG_INFO_SUCCESS_STEP, HG_INFO_RESET = 1, 2, 4, 8, 16
+HG_FAIL_CONTACT, HG_FAIL_SINK, HG_FAIL_ROLL, HG_FAIL_PITCH, HG_FAIL_NS, HG_FAIL_EW, HG_FAIL_CEILING = 1, 2, 4, 8, 16, 32, 64
+HG_FAIL_FAILED = 128
 HG_RESET_TEMPLATE, HG_RESET_RETRIM = 0, 1
 RESET_MODES = {"template": HG_RESET_TEMPLATE, "retrim": HG_RESET_RETRIM}
 HG_AUTORESET_SAME_STEP, HG_AUTORESET_NEXT_STEP = 0, 1
@@ -207,6 +209,9 @@ _SIGS = {
     "hg_debug_eta": (ctypes.c_int32, [_P, _P, _P]),
     "hg_debug_philox": (ctypes.c_int32, [_P, _P, ctypes.c_int64, _P]),
     "hg_debug_task": (ctypes.c_int32, [_P, _P, _P, _P, _P, ctypes.c_int64, _P]),
+    "hg_debug_failed": (ctypes.c_int32, [_P, _P, _P, _P, _P, ctypes.c_int64, _P]),
+    "hg_debug_failed_host": (ctypes.c_int32, [ctypes.POINTER(hg_config), _P, ctypes.c_int32, ctypes.c_int32, _P, _P,
+                                              ctypes.c_int64, _P, _P]),
     "hg_debug_task_host": (ctypes.c_int32, [ctypes.POINTER(hg_config), _P, _P, ctypes.POINTER(hg_target), ctypes.c_int64,
                                             _P, _P]),
     "hg_trim_conds_batch": (ctypes.c_int32, [_P, ctypes.POINTER(hg_trim_cond), ctypes.c_int64, _P, _P, _P, _P,

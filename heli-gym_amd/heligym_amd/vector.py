@@ -1753,6 +1753,21 @@ class HeliVecEnv(*_VEC_BASES):
         self._check(self.lib.hg_debug_task(self._h, _ptr(heli), _ptr(dots), _ptr(rew), _ptr(succ), n, self._stream()))
         return out
 
+    def debug_failed(self, heli, dots):
+        """Diagnostic: the failure test alone (hg_debug_failed) on rows of post-step heli state [n,18] and k4
+        derivatives [n,18], float32 on the env's device: (failed [n] uint8, clauses [n] uint8 of HG_FAIL_* bits)
+        with the env's constants and terrain, or, under a fleet, row i with the class of env i % num_envs."""
+        t = self.torch
+        n = int(heli.shape[0])
+        for name, x in (("heli", heli), ("dots", dots)):
+            if (tuple(x.shape) != (n, 18) or x.dtype != t.float32 or x.device != t.device(self.device)
+                    or not x.is_contiguous()):
+                raise ValueError(f"debug_failed: {name} must be a contiguous float32 ({n}, 18) tensor on {self.device}")
+        failed = t.empty((n,), dtype=t.uint8, device=self.device)
+        clauses = t.empty((n,), dtype=t.uint8, device=self.device)
+        self._check(self.lib.hg_debug_failed(self._h, _ptr(heli), _ptr(dots), _ptr(failed), _ptr(clauses), n, self._stream()))
+        return failed, clauses
+
     def random_actions(self, out, seed, step, lo=-1.0, hi=1.0):
         self._check(self.lib.hg_random_actions(self._h, _ptr(out), int(seed), int(step), float(lo),
                                                float(hi), self._stream()))
@@ -1781,6 +1796,24 @@ def task_reward_host(cfg, heli, dots, goals=None):
     _abi.check(lib.hg_debug_task_host(ctypes.byref(cfg), h.ctypes.data, d.ctypes.data, arr, n, rew.ctypes.data,
                                       succ.ctypes.data), lib)
     return rew, succ.astype(bool)
+
+
+def is_failed_host(cfg, terrain, heli, dots):
+    """Diagnostic, no device: Heli._is_failed in fp64 on the host (hg_debug_failed_host) for rows of post-step heli
+    state [n,18] and k4 derivatives [n,18] under `cfg` over `terrain` [rows, cols] ft: (failed [n] bool, clauses [n]
+    uint8 of HG_FAIL_* bits)."""
+    lib = _abi.load_library()
+    h = np.ascontiguousarray(heli, dtype=np.float64)
+    d = np.ascontiguousarray(dots, dtype=np.float64)
+    if h.ndim != 2 or h.shape[1] != 18 or d.shape != h.shape:
+        raise ValueError("is_failed_host: heli and dots must be [n, 18]")
+    ter = np.ascontiguousarray(terrain, dtype=np.float64)
+    n = h.shape[0]
+    failed = np.empty(n, dtype=np.uint8)
+    clauses = np.empty(n, dtype=np.uint8)
+    _abi.check(lib.hg_debug_failed_host(ctypes.byref(cfg), ter.ctypes.data, ter.shape[0], ter.shape[1], h.ctypes.data,
+                                        d.ctypes.data, n, failed.ctypes.data, clauses.ctypes.data), lib)
+    return failed.astype(bool), clauses
 
 
 def _airframe_fields(af):

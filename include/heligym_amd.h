@@ -71,6 +71,12 @@ enum { HG_RESET_TEMPLATE = 0, HG_RESET_RETRIM = 1 };
 enum { HG_AUTORESET_SAME_STEP = 0, HG_AUTORESET_NEXT_STEP = 1 };
 
 /* info bit-field written per env by hg_step (helicopter.py:219-224). */
+/* hg_debug_failed / hg_debug_failed_host: the clauses of Heli._is_failed (helicopter.py:226-234) that hold for a
+ * row, whether or not they fail it: failed = (CONTACT and (SINK or ROLL or PITCH)) or NS or EW or CEILING.
+ * HG_FAIL_FAILED: that combination as the function that reports the clauses forms it (a copy of the step
+ * kernels' test, which returns `failed`; the two are equal on every row). */
+enum { HG_FAIL_CONTACT = 1, HG_FAIL_SINK = 2, HG_FAIL_ROLL = 4, HG_FAIL_PITCH = 8, HG_FAIL_NS = 16, HG_FAIL_EW = 32,
+       HG_FAIL_CEILING = 64, HG_FAIL_FAILED = 128 };
 enum { HG_INFO_FAILED = 1, HG_INFO_SUCCESSED = 2, HG_INFO_TIME_UP = 4, HG_INFO_SUCCESS_STEP = 8,
        HG_INFO_RESET = 16 /* auto-reset at the end of this step (same-step auto-reset) */ };
 
@@ -919,6 +925,12 @@ int32_t hg_goal_draw(const hg_config* cfg, const hg_goal_box* box, int64_t globa
  * reward [n], success [n] (0 / 1).  HG_TASK_HELI is refused. */
 int32_t hg_debug_task_host(const hg_config* cfg, const double* heli, const double* dots, const hg_target* goals,
                            int64_t n, double* reward, uint8_t* success);
+/* Diagnostic, host only, fp64: Heli._is_failed (the function the step kernels instantiate in fp32) on n rows of
+ * post-step heli state [n,18] and k4 derivatives [n,18], with the ground height of `terrain_ft` [rows, cols] under
+ * each row's position and the constants of a handle configured as cfg.  failed [n] (0 / 1), clauses [n]
+ * (HG_FAIL_* bits). */
+int32_t hg_debug_failed_host(const hg_config* cfg, const double* terrain_ft, int32_t rows, int32_t cols,
+                             const double* heli, const double* dots, int64_t n, uint8_t* failed, uint8_t* clauses);
 
 /* ---- Mixed fleets: airframes that differ across one handle's envs, one airframe class per 64-env state tile.
  *
@@ -1048,6 +1060,13 @@ int32_t hg_debug_eta(hg_env* env, float* eta_dev, void* stream);
  * it changes no state of the handle.  HG_TASK_HELI is refused. */
 int32_t hg_debug_task(hg_env* env, const float* heli_dev, const float* dots_dev, float* reward_dev,
                       uint8_t* success_dev, int64_t n, void* stream);
+
+/* Diagnostic (parity tests): the failure test alone, fp32, on n rows of post-step heli state heli_dev [n,18] and k4
+ * derivatives dots_dev [n,18]: the function the step kernels call, with the handle's device constants and terrain
+ * texels; under a fleet, row i with the constants of the class of env i % N.  failed_dev [n] u8 (0 / 1),
+ * clauses_dev [n] u8 (HG_FAIL_* bits).  n is any count >= 0; it changes no state of the handle. */
+int32_t hg_debug_failed(hg_env* env, const float* heli_dev, const float* dots_dev, uint8_t* failed_dev,
+                        uint8_t* clauses_dev, int64_t n, void* stream);
 
 /* Diagnostic (known-answer tests): the device Philox4x32-10 on `count` rows of in_dev
  * {ctr0, ctr1, ctr2, ctr3, key0, key1} (u32) -> out_dev [count,4] u32.  It has no handle: it runs on

@@ -716,17 +716,42 @@ int or_task_reward(const or_model* m, int task, const hg_target* target, const d
     return 0;
 }
 
-/* Heli._is_failed (helicopter.py:226-234), post-step state and k4 dots. */
-int or_is_failed(const or_model* m, const double s[18], const double d[18]) {
+/* Heli._is_failed (helicopter.py:226-234), post-step state and k4 dots, under NumPy 2's promotion rules (the
+ * dtypes are recorded in tests/golden/fail_kats.npz).  While the state array is float32 (state_f32: at reset and
+ * until the first step ends, dynamics.py:168) `state[...] > python float` compares in float32: roll, pitch and
+ * |x|, |y| against the threshold rounded to float32.  state_dots is float64 always, so the sink rate compares in
+ * fp64; the terrain height is float64 (a float64 map), so contact and the ceiling do too, with x_loc, y_loc formed
+ * in float32 while the state is.  `clauses` (or NULL): HG_FAIL_* bits of the clauses that hold.  Returns -1 for a
+ * NaN x or y: the reference raises there (math.floor of a NaN, helicopter_dynamics.py:185). */
+int or_is_failed_p(const or_model* m, const double s[18], const double d[18], int state_f32, int32_t* clauses) {
     const hg_airframe* a = &m->cfg.af;
-    double gta = ground_touching_altitude(m, s[15], s[16], 0);
+    if (clauses) *clauses = 0;
+    if (isnan(s[15]) || isnan(s[16])) return -1;
+    double gta = ground_touching_altitude(m, s[15], s[16], state_f32);
+    double ang = 60 * D2R, ns = a->env_NS_MAX / 2, ew = a->env_EW_MAX / 2;
     int c1 = (-s[17]) - gta < 0.0;
     int c2 = d[17] > m->mr_VTIP * 0.05;
-    int c3 = s[12] > 60 * D2R;
-    int c4 = s[13] > 60 * D2R;
-    int c5 = fabs(s[15]) > a->env_NS_MAX / 2 || fabs(s[16]) > a->env_EW_MAX / 2 || -s[17] > gta + 10000;
-    return (c1 && (c2 || c3 || c4)) || c5;
+    int c3, c4, c5n, c5e;
+    if (state_f32) {
+        c3 = (float)s[12] > (float)ang;
+        c4 = (float)s[13] > (float)ang;
+        c5n = fabsf((float)s[15]) > (float)ns;
+        c5e = fabsf((float)s[16]) > (float)ew;
+    } else {
+        c3 = s[12] > ang;
+        c4 = s[13] > ang;
+        c5n = fabs(s[15]) > ns;
+        c5e = fabs(s[16]) > ew;
+    }
+    int c5t = -s[17] > gta + 10000;
+    if (clauses)
+        *clauses = (c1 ? HG_FAIL_CONTACT : 0) | (c2 ? HG_FAIL_SINK : 0) | (c3 ? HG_FAIL_ROLL : 0) | (c4 ? HG_FAIL_PITCH : 0) |
+                   (c5n ? HG_FAIL_NS : 0) | (c5e ? HG_FAIL_EW : 0) | (c5t ? HG_FAIL_CEILING : 0);
+    return (c1 && (c2 || c3 || c4)) || c5n || c5e || c5t;
 }
+
+/* the post-step form (a float64 state) */
+int or_is_failed(const or_model* m, const double s[18], const double d[18]) { return or_is_failed_p(m, s, d, 0, NULL); }
 
 /* ------------------------------------------------------------------ env step / reset */
 
@@ -860,7 +885,7 @@ int or_trim(const or_model* m, const hg_trim_cond* tc, const double W[3], hg_tri
     for (int i = 0; i < 4; i++) out->action[i] = x[12 + i];
     out->residual = tol;
     out->iterations = it;
-    out->failed = or_is_failed(m, out->state, out->state_dots);
+    out->failed = or_is_failed_p(m, out->state, out->state_dots, 1, NULL);   /* reset time: a float32 state */
     return HG_OK;
 }
 

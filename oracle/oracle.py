@@ -68,6 +68,8 @@ class Oracle:
         lib.or_heli_step.argtypes = [ctypes.c_void_p, PD, PD, PD, PD, PD, ctypes.c_int]
         lib.or_is_failed.restype = ctypes.c_int
         lib.or_is_failed.argtypes = [ctypes.c_void_p, PD, PD]
+        lib.or_is_failed_p.restype = ctypes.c_int
+        lib.or_is_failed_p.argtypes = [ctypes.c_void_p, PD, PD, ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]
         lib.or_step.argtypes = [ctypes.c_void_p, ctypes.POINTER(or_env), PD, PD, ctypes.POINTER(or_out)]
         lib.or_trim.restype = ctypes.c_int
         lib.or_trim.argtypes = [ctypes.c_void_p, ctypes.POINTER(_abi.hg_trim_cond), PD,
@@ -172,6 +174,20 @@ class Oracle:
         if rc != 0:
             raise ValueError(f"oracle: task {task!r} has no reward")
         return rew, succ.astype(bool)
+
+    def is_failed(self, heli, dots, state_f32=False):
+        """Heli._is_failed alone (or_is_failed_p) for rows of state [n,18] and k4 derivatives [n,18]: (failed [n]
+        int8, clauses [n] uint8 of HG_FAIL_* bits).  state_f32: the state is the reference's float32 array (reset
+        time) rather than its float64 one (after a step).  failed is -1 where the reference raises (NaN x or y)."""
+        h = np.ascontiguousarray(heli, dtype=np.float64).reshape(-1, 18)
+        d = np.ascontiguousarray(dots, dtype=np.float64).reshape(-1, 18)
+        failed = np.zeros(len(h), dtype=np.int8)
+        clauses = np.zeros(len(h), dtype=np.uint8)
+        bits = ctypes.c_int32()
+        for i in range(len(h)):
+            failed[i] = self.lib.or_is_failed_p(self.m, _dp(h[i]), _dp(d[i]), int(bool(state_f32)), ctypes.byref(bits))
+            clauses[i] = bits.value
+        return failed, clauses
 
     def set_stage_f32(self, on):
         """Diagnostic: RK stage inputs and the updated state rounded to float32 (an fp32

@@ -320,3 +320,126 @@ def load_variant(name):
     doc = copy.deepcopy(config.load_airframe("aw109"))
     doc["airframe"].update(json.loads(str(d["airframe_edits_json"])))
     return d, doc
+
+
+# ------------------------------------------------------------------------------------------------
+# Heli._is_failed (helicopter.py:226-234): fail_kats.npz, fail_traj.npz
+
+FAIL_CLAUSES = ("contact", "sink", "roll", "pitch", "ns", "ew", "ceiling")   # bit i of a clause byte (HG_FAIL_*)
+FAIL_BIT = {c: 1 << i for i, c in enumerate(FAIL_CLAUSES)}
+HMAP_H_TOL = 0.0   # ft: tests/test_oracle_golden.py holds the terrain height hmap_h to the reference exactly
+
+
+def fail_margin(alt):
+    """How close to its threshold the altitude of a terrain clause (contact: gta, ceiling: gta + 10000) may lie
+    before the clause counts as ambiguous: the suite's tolerance on the interpolated terrain height plus one fp32
+    ulp of the altitude."""
+    with np.errstate(all="ignore"):
+        return HMAP_H_TOL + np.spacing(np.abs(np.asarray(alt, dtype=np.float64)).astype(np.float32)).astype(np.float64)
+
+
+def fail_inside(alt, gta):
+    """[n, 2] bool: the contact / the ceiling clause of each row lies inside fail_margin of the reference's own gta."""
+    alt, gta = np.asarray(alt, dtype=np.float64), np.asarray(gta, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        m = fail_margin(alt)
+        return np.stack([np.abs(alt - gta) <= m, np.abs(alt - gta - 10000.0) <= m], axis=1)
+
+
+def half_extent(airframe=None):
+    """(NS_MAX / 2, EW_MAX / 2) ft of an airframe document (default: the bundled AW109): beyond it _is_failed's
+    bounds clause fires."""
+    from heligym_amd import config
+    af = (airframe or config.load_airframe("aw109"))["airframe"]
+    return float(af["env_NS_MAX"]) / 2, float(af["env_EW_MAX"]) / 2
+
+
+def north_out(airframe=None):
+    """A north position (ft) past the map's half-extent by about 20 ft, so that the NS clause alone fails an env."""
+    return float(np.ceil(half_extent(airframe)[0] + 19.0))
+
+
+def fail_airframe(edits_json):
+    """The airframe document a fail_kats.npz airframe was recorded with: the bundled AW109 with the edits."""
+    import copy
+    import json
+    from heligym_amd import config
+    doc = copy.deepcopy(config.load_airframe("aw109"))
+    doc["airframe"].update(json.loads(str(edits_json)))
+    return doc
+
+
+def load_fail_kats(airframe):
+    """fail_kats.npz for one airframe: heli, dots [n,18] float64 (fp32 values), failed, hit, raises, gta, clauses,
+    label, kind, inside [n,2], doc (the airframe document), dtypes."""
+    d = _npz(os.path.join(GOLDEN, "fail_kats.npz"))
+    k = {key: d[f"{airframe}/{key}"] for key in ("failed", "hit", "raises", "gta", "clauses", "kind", "inside", "thresholds")}
+    k["heli"], k["dots"] = d[f"{airframe}/heli"].astype(np.float64), d[f"{airframe}/dots"].astype(np.float64)
+    k["label"] = np.array([str(s) for s in d[f"{airframe}/label"]])
+    k["doc"] = fail_airframe(d[f"{airframe}/airframe_edits_json"])
+    k["dtypes"] = {key: str(d[key]) for key in ("gta_dtype", "altitude_minus_gta_dtype", "euler_compare_dtype",
+                                                "zdot_compare_dtype", "state_dtype", "state_dots_dtype")}
+    return k
+
+
+def check_fail_kats(k, failed, clauses, who):
+    """The agreement contract on fail_kats.npz.  The single-component clauses (sink, roll, pitch, NS, EW) agree with
+    the reference on every row, the fp32 threshold rows included.  Contact and ceiling agree on every row outside
+    fail_margin of the reference's own gta; inside it only that clause's bit may differ.  `failed` agrees wherever
+    every clause bit does.  Rows on which the reference raises (NaN x or y) are not compared.  Returns (rows whose
+    contact bit differs, rows whose ceiling bit differs, least |altitude - threshold| / margin among agreeing
+    terrain-clause decisions)."""
+    failed, clauses = np.asarray(failed).astype(bool), np.asarray(clauses).astype(np.uint8)
+    ok = ~k["raises"]
+    diff = (clauses ^ k["clauses"]) & 127
+    single = sum(FAIL_BIT[c] for c in ("sink", "roll", "pitch", "ns", "ew"))
+    bad = np.nonzero(ok & ((diff & single) != 0))[0]
+    assert len(bad) == 0, (who, "single-component clause", [(i, k["label"][i], int(clauses[i]), int(k["clauses"][i])) for i in bad[:10]])
+    n_diff = []
+    for col, c in ((0, "contact"), (1, "ceiling")):
+        d = ok & ((diff & FAIL_BIT[c]) != 0)
+        bad = np.nonzero(d & ~k["inside"][:, col])[0]
+        alt = -k["heli"][:, 17]
+        assert len(bad) == 0, (who, c, [(i, k["label"][i], alt[i] - k["gta"][i] - (10000.0 if col else 0.0)) for i in bad[:10]])
+        n_diff.append(int(d.sum()))
+    bad = np.nonzero(ok & (diff == 0) & (failed != k["failed"]))[0]
+    assert len(bad) == 0, (who, "failed", [(i, k["label"][i]) for i in bad[:10]])
+    return n_diff[0], n_diff[1]
+
+
+def load_fail_traj():
+    """fail_traj.npz as {scenario: {dt, fails, action, eta, init_*, failed, terminated, ..., clauses, gta, heli, dots
+    (post-step rows with the recorded columns filled in, the rest 0)}}."""
+    d = _npz(os.path.join(GOLDEN, "fail_traj.npz"))
+    cols = d["cols"]
+    out = {}
+    for s in (str(x) for x in d["scenarios"]):
+        T = len(d[f"{s}/action"])
+        e = {"dt": float(d["dt"]), "fails": bool(d[f"{s}/fails"]), "heli": np.zeros((T, 18)), "dots": np.zeros((T, 18))}
+        e["heli"][:, cols], e["dots"][:, 17] = d[f"{s}/state_cols"], d[f"{s}/zdot"]
+        for key in ("action", "eta", "init_state", "init_wind_state", "init_obs", "init_state_dots", "init_trim_cond",
+                    "failed", "successed", "time_up", "terminated", "truncated", "clauses", "gta"):
+            e[key] = d[f"{s}/{key}"]
+        out[s] = e
+    return out
+
+
+def fail_traj_determinate(heli, dots, gta, thresholds, scale=1.0):
+    """Whether `failed` of every recorded step of a free-running episode is the same for every implementation within
+    the trajectory tolerance, scaled by `scale`: positions (x, y, altitude), which only integrate, within
+    (t + 1) fp32 ulps at step t (one rounding of the stored state per step) plus the terrain margin; roll, pitch
+    and the sink rate within contract (ii).  A clause within tolerance of its threshold counts both ways.
+    thresholds: (V_TIP * 0.05, 60 deg, NS_MAX / 2, EW_MAX / 2)."""
+    heli, dots = np.asarray(heli, dtype=np.float64), np.asarray(dots, dtype=np.float64)
+    t_sink, t_ang, t_ns, t_ew = thresholds[:4]
+    steps = np.arange(len(heli)) + 1.0
+    alt = -heli[:, 17]
+    pos = lambda v: scale * (steps * fail_margin(v))  # noqa: E731
+    vals = [(gta - alt, pos(alt)), (dots[:, 17] - t_sink, scale * _traj_tol(dots[:, 17])),
+            (heli[:, 12] - t_ang, scale * _traj_tol(heli[:, 12])), (heli[:, 13] - t_ang, scale * _traj_tol(heli[:, 13])),
+            (np.abs(heli[:, 15]) - t_ns, pos(heli[:, 15])), (np.abs(heli[:, 16]) - t_ew, pos(heli[:, 16])),
+            (alt - gta - 10000.0, pos(alt))]
+    lo = [v > tol for v, tol in vals]     # holds for certain
+    hi = [v > -tol for v, tol in vals]    # may hold
+    f = lambda c: (c[0] & (c[1] | c[2] | c[3])) | c[4] | c[5] | c[6]  # noqa: E731
+    return bool(np.array_equal(f(lo), f(hi)))

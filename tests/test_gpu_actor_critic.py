@@ -16,6 +16,7 @@ Run with -m gpu."""
 import numpy as np
 import pytest
 
+import golden_cases as gc
 from test_gpu_noise import ETA_ABS, ETA_REL
 from test_gpu_policy_rollout import (NAMES, RESET_BIT, SEED, _assert_same, _env, _golden_obs, _on_device, _set,   # noqa: F401
                                      _z_ref, policy, torch)
@@ -25,7 +26,7 @@ pytestmark = pytest.mark.gpu
 K = 12
 AC_NAMES = ("logp", "value", "next_value")
 LN_2PI_X2 = 2.0 * np.log(2.0 * np.pi)
-NORTH_OUT = 3300.0   # ft: past the map's half-extent (6561.68 / 2), so is_failed's bounds clause fires
+NORTH_OUT = gc.north_out()   # ft: past the airframe's NS half-extent, so is_failed's bounds clause fires
 
 
 @pytest.fixture(scope="module")

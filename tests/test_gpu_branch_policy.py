@@ -19,6 +19,7 @@ Run with -m gpu."""
 import numpy as np
 import pytest
 
+import golden_cases as gc
 from test_gpu_branch_rollout import (BRANCHES, DEV, H, N, RESET_BIT, _assert_same, _checked, _env, _return32, _trim,   # noqa: F401
                                      torch)
 from test_gpu_policy_rollout import _golden_obs
@@ -27,7 +28,7 @@ pytestmark = pytest.mark.gpu
 
 GAMMAS = (1.0, 0.5, 0.99)
 BOOTS = ((False, 1.0), (True, 1.0), (True, 0.25), (True, 3.7))   # (bootstrap, value_scale)
-NORTH_OUT = 3300.0   # ft: past the map's half-extent (6561.68 / 2), so is_failed's bounds clause fires
+NORTH_OUT = gc.north_out()   # ft: past the airframe's NS half-extent, so is_failed's bounds clause fires
 FAILED, SUCCESSED, TIME_UP = 1, 2, 4
 
 
